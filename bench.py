@@ -4,7 +4,13 @@
 Headline (BASELINE.json metric, config 2): frames/sec of the unguided NConv U-Net (DNET /
 SETP1_NCONV, models/step1.py:15-94) forward on B=8 synthetic KITTI-shaped 352x1216 sparse depth
 per GPU, inputs resident in HBM, computed in EXACT fp32 (every product an fp32 product, as the
-reference's F.conv2d; include/nconv.h NCONV_MATH_FP32). Also on the same JSON line:
+reference's F.conv2d; include/nconv.h NCONV_MATH_FP32). A plain run sets up, warms up, times
+--steps graph replays of that forward, writes its outputs when --dump-outputs DIR is given and prints
+the result line (ms_per_step = the milliseconds one timed step took). --dump-outputs DIR writes what
+the last timed step computed, DIR/estimated_depth.npy (float32, the (B, 1, H, W) tensor a caller of
+the forward receives; a fixed seeded sample of it above 64 MB); the inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output. With --full, also on the
+same JSON line (null in a plain run):
   fwd_bf16x3         the same forward with split-bf16 matrix-core products (NCONV_MATH_BF16X3,
                      <= ~1.1e-5 relative per product: narrower than fp32, reported separately)
   config5            B=16 1024x2048 forward (BASELINE configs[4]), both arithmetics, own roofline
@@ -20,6 +26,7 @@ reference's F.conv2d; include/nconv.h NCONV_MATH_FP32). Also on the same JSON li
                      workload (B=8, generalized crop) and config 1 (3-layer forward, B=1)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--height 352] [--width 1216]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      # one process per GPU, RCCL
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N rank processes
@@ -75,6 +82,12 @@ def parse(argv=None):
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--height", type=int, default=352)
     p.add_argument("--width", type=int, default=1216)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the other arithmetics, config 5, the "
+                        "training and guided legs, per-kernel times and rooflines, the CPU baseline (the "
+                        "--no-* / --alt-math / --head-density options below select among them)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB)")
     p.add_argument("--train-steps", type=int, default=None, help="timed fwd+bwd steps (default: --steps)")
     p.add_argument("--no-train", action="store_true")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -103,6 +116,11 @@ def parse(argv=None):
                    help="replay the training step from a hipGraph (1, every world size: the RCCL all-reduce is "
                         "captured in the graph) or eager (0); on one GPU the eager step is reported beside it")
     a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if not a.full:  # a plain run: the headline only
+        a.alt_math, a.head_density = [], 0.0
+        a.no_config5 = a.no_train = a.no_guided = a.no_guided_train = a.no_cpu_baseline = True
     if a.inference_shares is not None and len(a.inference_shares) != (a.inference_streams or 2):
         p.error(f"--inference-shares has {len(a.inference_shares)} entries for {a.inference_streams or 2} "
                 "inference streams")
@@ -172,6 +190,25 @@ def sparse_depth(g, B, H, W, device, density=0.05):
     d = torch.rand(B, 1, H, W, generator=g) * 79 + 1
     d = d * (torch.rand(B, 1, H, W, generator=g) < density)
     return d.to(device)
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one rank together
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: each tensor of `arrays` as dirname/<name>.npy (rank 0; <name>_rank<r>.npy on the
+    other ranks), float32 (float64 stays float64). An output larger than its share of DUMP_MAX_BYTES
+    is written as a fixed sample: the elements at sorted flat indices drawn without replacement by
+    numpy's default_rng(0), the same indices for the same shape on every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        x = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).contiguous().numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (".npy" if rank == 0 else f"_rank{rank}.npy")), x)
 
 
 WARMUP_MIN_S = 0.2  # untimed warm-up per leg: at least --warmup calls and at least this long
@@ -714,12 +751,16 @@ def main():
     warm = {}
     math_key = lambda mth, Sx: f"{mth}:{'x'.join(map(str, Sx.shape))}"
 
-    def time_forward(Sx, steps, math):
+    kept = {}
+
+    def time_forward(Sx, steps, math, keep=False):
         """Warm-up passes (hipGraph capture when --graph; then replays for at least --warmup calls
         and WARMUP_MIN_S seconds), then `steps` timed passes between barrier + synchronize; returns
-        the max over ranks of the timed seconds."""
+        the max over ranks of the timed seconds. keep: after the clock has stopped, a host copy of
+        the last timed pass's output is left in kept["out"]."""
         m.nconv.FORWARD_MATH = math
         graph = None
+        last = {}
         with torch.no_grad():
             for _ in range(max(a.warmup, 1)):
                 net(Sx)
@@ -732,8 +773,8 @@ def main():
                 torch.cuda.current_stream().wait_stream(s)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    net(Sx)
-            one = graph.replay if graph is not None else (lambda: net(Sx))
+                    last["out"] = net(Sx)
+            one = graph.replay if graph is not None else (lambda: last.__setitem__("out", net(Sx)))
             warm[math_key(math, Sx)] = warm_up(one, a.warmup)
         torch.cuda.synchronize()
         barrier()
@@ -745,7 +786,9 @@ def main():
         torch.cuda.synchronize()
         barrier()
         el = time.perf_counter() - t0
-        del graph
+        if keep:
+            kept["out"] = last["out"].detach().cpu()
+        del graph, last
         return max_over_ranks(el)
 
     MATHS = {"fp32": lib.MATH_FP32, "bf16x9": lib.MATH_BF16X9, "bf16x3": lib.MATH_BF16X3}
@@ -756,14 +799,16 @@ def main():
     # ---- headline: config 2 forward ----
     log(f"config 2 forward, {a.math}")
     state0 = gpu_state(dev)
-    t_fwd = time_forward(S, a.steps, HEAD)
+    t_fwd = time_forward(S, a.steps, HEAD, keep=a.dump_outputs is not None)
     state1 = gpu_state(dev)
     fps = world * B * a.steps / t_fwd
+    if a.dump_outputs is not None:
+        dump_outputs(a.dump_outputs, {"estimated_depth": kept.pop("out")}, rank)
     # per-kernel times of each forward right after its timed run (rank 0), so the roofline's kernel
     # time is taken in the same conditions as the headline, not after the heavier legs below
     lt_of = {}
     head_density = None
-    if rank == 0:
+    if rank == 0 and a.full:
         log("per-kernel times")
         m.nconv.FORWARD_MATH = HEAD
         lt_of[a.math] = time_layers(m, net, S)
@@ -937,8 +982,9 @@ def main():
                                                         "frames_per_sec": round(B * gts / t2, 2),
                                                         "arith": DENSE_ARITH[mm]}
 
-    # ---- per-kernel times, rooflines, CPU baseline (rank 0) ----
-    if rank == 0:
+    # ---- per-kernel times, rooflines, CPU baseline (rank 0, --full) ----
+    lt = roof = cpu = None
+    if rank == 0 and a.full:
         costs = kernel_costs(B, H, W)
         lt = lt_of[a.math]
         issued = (lambda k: mfma_issued_flops(k, B, H, W, a.math)) if a.math in MFMA_TERMS else None
@@ -979,10 +1025,10 @@ def main():
             c5["roofline"] = roofline(lt5, kernel_costs(16, 1024, 2048), a.math, 16, 1024, 2048)
             c5["whole_pass_hbm_frac"] = round(1169.4e6 * 16 / (c5["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
         m.nconv.FORWARD_MATH = lib.MATH_FP32
-        cpu = None
         if not a.no_cpu_baseline and world == 1:
             log("CPU baseline")
             cpu = cpu_baseline(B, H, W, a.cpu_seconds)
+    if rank == 0:
         result = {
             "metric": "frames/sec (352x1216 sparse depth, DNET NConv U-Net forward, B=8 per GPU)",
             "value": round(fps, 2), "unit": "frames/sec", "n_gpus": world, "steps": a.steps,
@@ -994,7 +1040,8 @@ def main():
                        "crop": "generalized [1:H+1,1:W+1]", "parallelism": f"frame-sharded x{world}",
                        "hipgraph": bool(a.graph), "fused_head": bool(a.fused_head)},
             "arith": MATH_ARITH[a.math],
-            "layer_us": {k: round(v, 2) for k, v in lt.items()},
+            "full": a.full,
+            "layer_us": {k: round(v, 2) for k, v in lt.items()} if lt is not None else None,
             "roofline": roof,
             "head_density": head_density,
             "warmup_replays": {k: {"calls": n, "seconds": round(t, 3)} for k, (n, t) in warm.items()},

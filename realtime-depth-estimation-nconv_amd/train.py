@@ -13,6 +13,7 @@ Cheap elementwise/reduction glue around the NConv path (PyTorch-ROCm ops), excep
 import os
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as F
 import torch.optim as optimizer
 
@@ -193,7 +194,14 @@ class GraphedTrainStep:
         new_state = [v for st in optimizer.state.values() for v in st.values() if torch.is_tensor(v)]
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
+        # With a process group up, the backend's watchdog thread polls the events of the warm-up's
+        # all-reduces (it retires a finished one only at its next poll, up to 100 ms later). Under
+        # the default "global" capture mode such an event query from another thread while this one
+        # captures is an error (hipErrorStreamCaptureUnsupported) that aborts the process, so the
+        # capture is then thread-local: only this thread's calls are checked. Without a group
+        # there is no such thread and the mode stays the default.
+        mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"
+        with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.static_loss = self._body(zero=False)
         with torch.no_grad():
             for t, v in zip(tensors, snap):

@@ -17,7 +17,7 @@ for v in $1; do
   for l in ${LAYERS:-nconv1 nconv2 down1 down2 down3 nconv4 nconv5 tail}; do
     NCONV_LIB=_exp/$v/libnconv.so timeout -k 10 120 python -u tools/fwd_layer_bench.py $l 30 2>/dev/null | sed "s/^/$v /" >> $out || stop $v-$l $?
   done
-  NCONV_LIB=_exp/$v/libnconv.so timeout -k 10 300 python -u bench.py --no-train --alt-math '' --no-config5 --no-guided \
+  NCONV_LIB=_exp/$v/libnconv.so timeout -k 10 300 python -u bench.py --full --no-train --alt-math '' --no-config5 --no-guided \
      --no-guided-train --no-cpu-baseline --steps 30 --warmup 5 > gpurun_out/ab_fwd_bench_$v.log 2>&1 || stop bench-$v $?
   python3 -c "import json; d=json.loads(open('gpurun_out/ab_fwd_bench_$v.log').read().strip().splitlines()[-1]); print('$v bench', d['value'], d['ms_per_step'], d.get('roofline',{}).get('frac'))" >> $out
 done

@@ -7,6 +7,6 @@ timeout -k 10 300 python3 -u tools/dense_microbench.py > gpurun_out/gfp_micro.lo
 cat gpurun_out/gfp_micro.log
 rm -rf gpurun_out/gfp_prof
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/gfp_prof -o run -- \
-    python3 bench.py --alt-math= --no-config5 --no-train --no-guided-train --no-cpu-baseline --steps 10 \
+    python3 bench.py --full --alt-math= --no-config5 --no-train --no-guided-train --no-cpu-baseline --steps 10 \
     > gpurun_out/gfp_prof.log 2>&1
 rc=$?; echo "prof rc=$rc"; exit $rc

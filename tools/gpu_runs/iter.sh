@@ -10,7 +10,7 @@ if [ -n "$sel" ]; then
       -p no:cacheprovider > gpurun_out/it_${tag}_pytest.log 2>&1
   rc=$?; tail -3 gpurun_out/it_${tag}_pytest.log; [ $rc -eq 0 ] || exit $rc
 fi
-args="--alt-math= --no-config5 --no-guided --no-guided-train --no-cpu-baseline $*"
+args="--full --alt-math= --no-config5 --no-guided --no-guided-train --no-cpu-baseline $*"
 timeout -k 10 300 python -u bench.py $args > gpurun_out/it_${tag}_bench.log 2>&1
 rc=$?; tail -1 gpurun_out/it_${tag}_bench.log | cut -c1-600; [ $rc -eq 0 ] || exit $rc
 rm -rf gpurun_out/it_${tag}_prof

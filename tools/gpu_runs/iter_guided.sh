@@ -7,7 +7,7 @@ tag=$1
 timeout -k 10 400 python -u -m pytest tests/test_gpu_guided.py tests/test_gpu_dense_train.py tests/test_gpu_dense.py \
     -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider > gpurun_out/itg_${tag}_pytest.log 2>&1
 rc=$?; tail -3 gpurun_out/itg_${tag}_pytest.log; [ $rc -eq 0 ] || exit $rc
-args="--alt-math= --no-config5 --no-train --no-cpu-baseline"
+args="--full --alt-math= --no-config5 --no-train --no-cpu-baseline"
 timeout -k 10 400 python -u bench.py $args > gpurun_out/itg_${tag}_bench.log 2>&1
 rc=$?; tail -1 gpurun_out/itg_${tag}_bench.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc
 rm -rf gpurun_out/itg_${tag}_prof
