@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NCONV_ABI_VERSION 22
+#define NCONV_ABI_VERSION 23
 
 /* How a layer's input (data x, confidence c) is produced from its source tensors. These are the
  * DNET glue ops fused into the layer's load stage (models/step1.py:53,61-90). */
@@ -473,7 +473,10 @@ typedef struct nconv_bn_train {
     float momentum, eps;
     int relu;                  /* 1: y = max(BN(x), 0)                                            */
     float* y;                  /* (B, C, H, W) forward output                                     */
-    float* mean;               /* (C) batch mean: written by the forward, read by the backward    */
+    float* mean;               /* (2 C) batch mean as two fp32 words, [c] + [C + c] (ABI 23: one
+                                  word is half an ulp of the mean off, which a channel of large
+                                  mean and small spread sees times invstd in every output):
+                                  written by the forward, read by the backward                    */
     float* invstd;             /* (C) 1/sqrt(biased batch variance + eps): likewise               */
 } nconv_bn_train;
 

@@ -7,11 +7,14 @@
 //             block per channel, chunks combined in a fixed tree order with Chan's formula:
 //             deterministic, no E[x^2] - E[x]^2 cancellation; running mean / unbiased running var),
 //             bn_apply (1 read + 1 write: y = [relu](gamma (x - mean) invstd + beta));
+//             the mean is carried as two fp32 words (hi + lo) from the chunks to bn_apply: one word
+//             is off by up to half an ulp of the mean, which a channel with a large mean and a small
+//             spread (the depth channel: 40 +- 0.05) sees multiplied by invstd in every output;
 //   backward: bn_bwd_stats (2 reads: per chunk sum g', sum g' (x - mean), sum (x - mean), g' = g
 //             masked by the recomputed ReLU), bn_bwd_finalize (fixed order, double), bn_bwd_apply
 //             (2 reads + 1 write: gx = gamma invstd (g' - sum g' / N - xhat sum g' xhat / N), formed
 //             in double per element).
-// Why double in the backward: the saved mean is the batch mean rounded to fp32, so fp32 xhat = (x -
+// Why double in the backward: the saved mean is the batch mean rounded to two fp32 words, so fp32 xhat = (x -
 // mean) invstd sums to N (mean_exact - mean) invstd instead of 0, and sum g' / N rounds likewise;
 // both leave gx with a systematic nonzero sum, which the preceding convolution's weight gradient
 // (sum gx * input, inputs with a large mean such as 0..255 RGB) multiplies by N. At 480x640 that
@@ -80,7 +83,9 @@ __device__ __forceinline__ void store_chunk(float* plane, int hw, int j, bool ve
     }
 }
 
-// part[(c * nparts + b * ncp + j) * 3 + {0,1,2}] = (count, mean, M2) of chunk j of plane (b, c)
+// part[(c * nparts + b * ncp + j) * 4 + {0,1,2,3}] = (count, m, M2 about m, sum (x - m) / count) of
+// chunk j of plane (b, c): m is the fp32 sum / count, the chunk's mean m + the last word (the
+// differences x - m are exact or nearly so, and their sum is small)
 __global__ __launch_bounds__(kBT) void bn_stats(const float* __restrict__ x, int C, int hw, int ncp, int nparts,
                                                 int vec, float* __restrict__ part) {
     __shared__ float red[4];
@@ -94,18 +99,21 @@ __global__ __launch_bounds__(kBT) void bn_stats(const float* __restrict__ x, int
 #pragma unroll
     for (int k = 0; k < kPer; ++k) s += v[k];  // invalid elements are 0
     const float mean = block_sum(s, red) / (float)n;
-    float m2 = 0.f;
+    float m2 = 0.f, sd = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
         const float d = ok[k] ? v[k] - mean : 0.f;
         m2 = fmaf(d, d, m2);
+        sd += d;
     }
     m2 = block_sum(m2, red);
+    sd = block_sum(sd, red);
     if (threadIdx.x == 0) {
-        float* o = part + ((size_t)c * nparts + (size_t)b * ncp + j) * 3;
+        float* o = part + ((size_t)c * nparts + (size_t)b * ncp + j) * 4;
         o[0] = (float)n;
         o[1] = mean;
         o[2] = m2;
+        o[3] = sd / (float)n;
     }
 }
 
@@ -126,10 +134,13 @@ __global__ __launch_bounds__(kBT) void bn_finalize(const float* __restrict__ par
                                                    float* __restrict__ mean_out, float* __restrict__ invstd_out) {
     __shared__ double sn[kBT], sm[kBT], s2[kBT];
     const int c = blockIdx.x, t = threadIdx.x;
-    const float* p = part + (size_t)c * nparts * 3;
+    const float* p = part + (size_t)c * nparts * 4;
     const int per = (nparts + kBT - 1) / kBT, k0 = t * per, k1 = min(nparts, k0 + per);
     double n = 0.0, mean = 0.0, m2 = 0.0;
-    for (int k = k0; k < k1; ++k) chan_combine(n, mean, m2, p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+    for (int k = k0; k < k1; ++k) {  // M2 about the chunk's mean m + lo: M2 about m less count lo^2
+        const double nb = p[4 * k], lo = p[4 * k + 3];
+        chan_combine(n, mean, m2, nb, (double)p[4 * k + 1] + lo, fmax((double)p[4 * k + 2] - nb * lo * lo, 0.0));
+    }
     sn[t] = n;
     sm[t] = mean;
     s2[t] = m2;
@@ -149,7 +160,9 @@ __global__ __launch_bounds__(kBT) void bn_finalize(const float* __restrict__ par
         mean = sm[0];
         m2 = s2[0];
         const double var = m2 / n;
-        mean_out[c] = (float)mean;
+        const float hi = (float)mean;
+        mean_out[c] = hi;
+        mean_out[C + c] = (float)(mean - (double)hi);
         invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
         if (rmean) rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * mean);
         if (rvar) rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * (n > 1.0 ? m2 / (n - 1.0) : var));
@@ -181,8 +194,13 @@ __device__ __forceinline__ void chan_sums(const float* p, int nparts, double (&o
     for (int q = 0; q < NV; ++q) out[q] = red[q][0];
 }
 
-__device__ __forceinline__ float bn_y(float x, float mu, float is, float g, float bt, bool relu) {
-    const float y = fmaf((x - mu) * is, g, bt);
+// x - mean with the two-word mean, and the pre-activation: the forward and the backward's
+// recomputed ReLU mask go through the same two functions, so they decide alike
+__device__ __forceinline__ float bn_centred(float x, float mu, float lo) { return (x - mu) - lo; }
+__device__ __forceinline__ float bn_pre(float d, float is, float g, float bt) { return fmaf(d * is, g, bt); }
+
+__device__ __forceinline__ float bn_y(float x, float mu, float lo, float is, float g, float bt, bool relu) {
+    const float y = bn_pre(bn_centred(x, mu, lo), is, g, bt);
     return relu ? fmaxf(y, 0.f) : y;
 }
 
@@ -194,17 +212,17 @@ __global__ __launch_bounds__(kBT) void bn_apply(const float* __restrict__ x, flo
                                                 const float* __restrict__ beta, int relu) {
     const int j = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
     const size_t off = ((size_t)b * C + c) * hw;
-    const float mu = mean[c], is = invstd[c], g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const float mu = mean[c], lo = mean[C + c], is = invstd[c], g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
     float v[kPer];
     bool ok[kPer];
     load_chunk(x + off, hw, j, vec != 0, v, ok);
 #pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = bn_y(v[k], mu, is, g, bt, relu);
+    for (int k = 0; k < kPer; ++k) v[k] = bn_y(v[k], mu, lo, is, g, bt, relu);
     store_chunk(y + off, hw, j, vec != 0, v);
 }
 
 // part[(c * nparts + b * ncp + j) * 3 + {0,1,2}] = (sum g', sum g' (x - mean), sum (x - mean)) of
-// chunk j of plane (b, c); mean = the forward's fp32 batch mean
+// chunk j of plane (b, c); mean = the forward's two-word batch mean
 __global__ __launch_bounds__(kBT) void bn_bwd_stats(const float* __restrict__ gy, const float* __restrict__ x, int C,
                                                     int hw, int ncp, int nparts, int vec,
                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -217,12 +235,12 @@ __global__ __launch_bounds__(kBT) void bn_bwd_stats(const float* __restrict__ gy
     bool ok[kPer];
     load_chunk(gy + off, hw, j, vec != 0, g, ok);
     load_chunk(x + off, hw, j, vec != 0, v, ok);
-    const float mu = mean[c], is = invstd[c], ga = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const float mu = mean[c], lo = mean[C + c], is = invstd[c], ga = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
     float s = 0.f, sx = 0.f, sd = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
-        const float d = v[k] - mu;
-        const float gg = (relu && !(fmaf(d * is, ga, bt) > 0.f)) ? 0.f : g[k];  // invalid: g = 0
+        const float d = bn_centred(v[k], mu, lo);
+        const float gg = (relu && !(bn_pre(d, is, ga, bt) > 0.f)) ? 0.f : g[k];  // invalid: g = 0
         s += gg;
         sx = fmaf(gg, d, sx);
         sd += ok[k] ? d : 0.f;
@@ -255,7 +273,7 @@ __global__ __launch_bounds__(kBT) void bn_bwd_finalize(const float* __restrict__
         const double s0 = v[0] / n, a = is * (sxh / n);
         sums[3 * c] = s0;
         sums[3 * c + 1] = a;
-        sums[3 * c + 2] = s0 - ((double)mean[c] + delta) * a;
+        sums[3 * c + 2] = s0 - ((double)mean[c] + (double)mean[C + c] + delta) * a;
         if (gbeta) gbeta[c] = (float)v[0];
         if (ggamma) ggamma[c] = (float)sxh;
     }
@@ -268,7 +286,7 @@ __global__ __launch_bounds__(kBT) void bn_bwd_apply(const float* __restrict__ gy
                                                     int relu, const double* __restrict__ sums) {
     const int j = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
     const size_t off = ((size_t)b * C + c) * hw;
-    const float mu = mean[c], is = invstd[c], ga = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const float mu = mean[c], lo = mean[C + c], is = invstd[c], ga = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
     const double f = (double)ga * (double)is, a = sums[3 * c + 1], k0 = sums[3 * c + 2];
     float g[kPer], v[kPer];
     bool ok[kPer];
@@ -276,7 +294,8 @@ __global__ __launch_bounds__(kBT) void bn_bwd_apply(const float* __restrict__ gy
     load_chunk(x + off, hw, j, vec != 0, v, ok);
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
-        const float gg = (relu && !(fmaf((v[k] - mu) * is, ga, bt) > 0.f)) ? 0.f : g[k];  // the forward's mask
+        const float pre = bn_pre(bn_centred(v[k], mu, lo), is, ga, bt);
+        const float gg = (relu && !(pre > 0.f)) ? 0.f : g[k];  // the forward's mask
         v[k] = (float)(f * ((double)gg - k0 - a * (double)v[k]));
     }
     store_chunk(gx + off, hw, j, vec != 0, v);
@@ -350,10 +369,11 @@ int launch_relu_bias_bwd(int B, int C, int H, int W, const float* g, const float
 // ------------------------------------------------------------------------------------------------
 static int bn_ncp(const nconv_bn_train& p) { return (p.H * p.W + kChunk - 1) / kChunk; }
 
-// per-chunk partials (3 floats each), then the backward's per-channel sums (3 doubles, 8-B aligned)
+// per-chunk partials (4 floats each in the forward, 3 in the backward), then the backward's
+// per-channel sums (3 doubles, 8-B aligned)
 static size_t bn_sums_offset(const nconv_bn_train& p) {
     const size_t nparts = (size_t)p.B * bn_ncp(p);
-    return (nparts * p.C * 3 * sizeof(float) + 7) & ~(size_t)7;
+    return (nparts * p.C * 4 * sizeof(float) + 7) & ~(size_t)7;
 }
 
 size_t bn_workspace_bytes(const nconv_bn_train& p) { return bn_sums_offset(p) + 3 * (size_t)p.C * sizeof(double); }

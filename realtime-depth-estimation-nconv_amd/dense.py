@@ -311,8 +311,8 @@ class BatchNormReLUFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, bn, relu):
         x = x.contiguous()
         C = x.shape[1]
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty_like(mean)
+        mean = torch.empty(2 * C, device=x.device, dtype=torch.float32)  # hi words, then lo words
+        invstd = torch.empty(C, device=x.device, dtype=torch.float32)
         y = torch.empty_like(x)
         if bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)

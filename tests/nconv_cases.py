@@ -1,4 +1,6 @@
 """Shared input builders and the oracle-side layer (glue + nconv2d) for the parity tests."""
+import functools
+
 import torch
 import torch.nn.functional as F
 
@@ -7,20 +9,23 @@ from oracle import nconv_ref as R
 PLAIN, THRESH, POOL2, UPCAT_SKIP_FIRST, UPCAT_UP_FIRST = 0, 1, 2, 3, 4
 
 
+def glue(mode, xa, ca, xb, cb, thresh=0.01):
+    """The reference's glue op in front of a layer: (x, c) as NConv2d.forward receives them."""
+    if mode == THRESH:
+        return xa, (xa > thresh).to(xa.dtype)
+    if mode == PLAIN:
+        return xa, ca
+    if mode == POOL2:
+        return F.max_pool2d(xa, 2, 2), F.max_pool2d(ca, 2, 2)
+    up = lambda t: F.interpolate(t, xa.shape[2:], mode="nearest")
+    if mode == UPCAT_SKIP_FIRST:
+        return torch.cat((xa, up(xb)), 1), torch.cat((ca, up(cb)), 1)
+    return torch.cat((up(xb), xa), 1), torch.cat((up(cb), ca), 1)
+
+
 def oracle_layer(mode, xa, ca, xb, cb, w, b, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups=1, thresh=0.01):
     """The reference's glue op followed by NConv2d.forward, on whatever device/dtype given."""
-    if mode == THRESH:
-        x, c = xa, (xa > thresh).to(xa.dtype)
-    elif mode == PLAIN:
-        x, c = xa, ca
-    elif mode == POOL2:
-        x, c = F.max_pool2d(xa, 2, 2), F.max_pool2d(ca, 2, 2)
-    else:
-        up = lambda t: F.interpolate(t, xa.shape[2:], mode="nearest")
-        if mode == UPCAT_SKIP_FIRST:
-            x, c = torch.cat((xa, up(xb)), 1), torch.cat((ca, up(cb)), 1)
-        else:
-            x, c = torch.cat((up(xb), xa), 1), torch.cat((up(cb), ca), 1)
+    x, c = glue(mode, xa, ca, xb, cb, thresh)
     return R.nconv2d(x, c, w, b, stride, pad, dil, groups)
 
 
@@ -60,4 +65,258 @@ LAYER_CASES = [
     ("generic_stride2", PLAIN, 4, 6, 3, 1, 2, 1, 1, (4, 29, 41), None),
     ("generic_dil2_groups2", PLAIN, 4, 6, 3, 2, 1, 2, 2, (4, 29, 41), None),
     ("generic_pool_c3", POOL2, 3, 5, 5, 2, 1, 1, 1, (3, 21, 30), None),
+    # one row and one column past a 16x32 tile; the exactly-2x UpCat likewise (low side 17x33)
+    ("nconv2_tile_plus1", PLAIN, 8, 8, 5, 2, 1, 1, 1, (8, 33, 65), None),
+    ("nconv4_upcat_tile_plus1", UPCAT_SKIP_FIRST, 16, 8, 3, 1, 1, 1, 1, (8, 34, 66), (8, 17, 33)),
 ]
+
+
+def r32(t):
+    """float64 tensor holding the fp32 rounding of t: the operand the GPU sees."""
+    return None if t is None else t.float().double()
+
+
+def build_case(case, seed):
+    """float64 operands (xa, ca, xb, cb, w, b) of a LAYER_CASES entry at batch 2."""
+    name, mode, cin, cout, k, pad, stride, dil, groups, a_shape, b_shape = case
+    g = torch.Generator().manual_seed(seed)
+    xa, ca = rand_pair(g, 2, *a_shape, dtype=torch.float64)
+    if mode == THRESH:
+        xa = xa * (torch.rand(xa.shape, generator=g, dtype=torch.float64) < 0.3)
+        ca = None
+    if name.endswith("_ties"):  # small integer values and a 3-level confidence: many exact ties
+        xa = torch.randint(0, 3, xa.shape, generator=g).double()
+        ca = torch.randint(0, 3, ca.shape, generator=g).double() * 0.5
+    xb = cb = None
+    if b_shape is not None:
+        xb, cb = rand_pair(g, 2, *b_shape, dtype=torch.float64)
+    w = rand_weight(g, cout, cin // groups, k, k, torch.float64)
+    b = torch.rand(cout, generator=g, dtype=torch.float64) * 0.1
+    return xa, ca, xb, cb, w, b
+
+
+# Exact-2x UPCAT layers on the phase path (nconv_layer.wphase, nconv_fwd_phase.hip): both channel
+# orders, paddings 0 / 1 / 2 (both phase parities), ragged widths, tiles cut by the image edge.
+# (name, mode, pad, a-shape, b-shape)
+PHASE_CASES = [
+    ("skip_p1", 3, 1, (8, 24, 70), (8, 12, 35)),
+    ("skip_p1_w4", 3, 1, (8, 26, 72), (8, 13, 36)),
+    ("skip_p0", 3, 0, (8, 20, 64), (8, 10, 32)),
+    ("skip_p2", 3, 2, (8, 18, 46), (8, 9, 23)),
+    ("up_p0", 4, 0, (8, 34, 72), (8, 17, 36)),
+    ("up_p1", 4, 1, (8, 36, 66), (8, 18, 33)),
+]
+
+
+# ------------------------------------------------------------------------------------------------
+# The element-wise gradient criterion: |got - ref| <= kappa * A + 1e-30 per element, ref the float64
+# oracle on fp32-rounded operands, A the majorant below, kappa from tests/golden/bwd_bound_kappa.json
+# (tools/bwd_kappa.py: the reference's own float32 run measured against the same float64 oracle).
+# ------------------------------------------------------------------------------------------------
+GRAD_LABELS = ("g_xa", "g_ca", "g_xb", "g_cb", "g_w", "g_b")
+KAPPA_FLOOR = 2.0 ** -22
+BF16X3_PER_PRODUCT = 1.1e-5  # include/nconv.h, NCONV_MATH_BF16X3
+TILE = (16, 32)              # output tile of the tiled kernels (rows, columns)
+
+
+def nconv2d_backward_majorant(x, c, w, b, gy, gcout, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups=1, eps=R.EPS):
+    """The closed form of oracle.nconv_ref.nconv2d_backward (here with dilation and groups) in float64,
+    every factor replaced by its absolute value and every subtraction by an addition: per element
+    the sum of the magnitudes of the terms a gradient is made of, so kappa * A is what a backward
+    with relative error kappa per term may be off by.
+
+        MN   = |gy| / (D+eps)
+        MD   = |gy| (|y| + |b|) / (D+eps) + |gcout| / s
+        A_xc = |W|^T (*) MN              A_x = A_xc |c|        A_c = A_xc |x| + |W|^T (*) MD
+        A_w  = wgrad(|x c|, MN) + wgrad(|c|, MD) + sum |gcout| D / s^2          A_b = sum |gy|
+
+    MD carries |y| + |b| rather than |N| / (D+eps): the backward recovers N / (D+eps) as y - b from
+    the saved fp32 output, and that cancellation's rounding, relative to |y| and |b|,
+    belongs in the budget. Returns (A_x, A_c, A_w, A_b) for the glued inputs x, c."""
+    from torch.nn.grad import conv2d_input, conv2d_weight
+    assert x.dtype == torch.float64
+    geo = (stride, pad, dil, groups)
+    aw, ab = w.abs(), b.abs().view(1, -1, 1, 1)
+    D = F.conv2d(c, w, None, *geo)
+    y = F.conv2d(x * c, w, None, *geo) / (D + eps) + b.view(1, -1, 1, 1)
+    s = w.reshape(w.shape[0], -1).sum(-1).view(1, -1, 1, 1)
+    inv = 1 / (D + eps).abs()
+    MN = gy.abs() * inv
+    MD = gy.abs() * (y.abs() + ab) * inv + gcout.abs() / s.abs()
+    A_xc = conv2d_input(x.shape, aw, MN, *geo)
+    A_x = A_xc * c.abs()
+    A_c = A_xc * x.abs() + conv2d_input(c.shape, aw, MD, *geo)
+    A_w = conv2d_weight((x * c).abs(), w.shape, MN, *geo) + conv2d_weight(c.abs(), w.shape, MD, *geo)
+    A_w = A_w + (gcout.abs() * D.abs() / s ** 2).sum((0, 2, 3)).view(-1, 1, 1, 1)
+    return A_x, A_c, A_w, gy.abs().sum((0, 2, 3))
+
+
+def glue_adjoint(mode, xa, ca, xb, cb, t_x, t_c, thresh=0.01):
+    """The glue's adjoint applied to (t_x, t_c), tensors shaped like the glued x and c: the max-pool
+    scatters to its first-maximum argmax, the nearest upsample sums each low pixel's children, the
+    concat splits. It is linear with 0 / 1 coefficients, so it carries gradients and majorants
+    alike. Returns (for xa, ca, xb, cb), None where the layer has no such input."""
+    if mode == PLAIN:
+        return t_x, t_c, None, None
+    if mode == THRESH:
+        return t_x, None, None, None
+    ins = [t.detach().clone().requires_grad_(True) if t is not None else None for t in (xa, ca, xb, cb)]
+    x, c = glue(mode, *ins, thresh)
+    live = [t for t in ins if t is not None]
+    got = iter(torch.autograd.grad([x, c], live, [t_x, t_c]))
+    return tuple(next(got) if t is not None else None for t in ins)
+
+
+class BwdProblem:
+    """One layer-backward comparison: fp32-rounded float64 operands, output gradients, geometry."""
+
+    def __init__(self, name, mode, ops, gy, gc, geom):
+        self.name, self.mode, self.ops, self.gy, self.gc, self.geom = name, mode, list(ops), gy, gc, geom
+        self.cin_g, self.k = ops[4].shape[1], ops[4].shape[2]
+
+    def grads(self, dtype=torch.float64):
+        """Autograd of the oracle's own op sequence in dtype; the six gradients as float64."""
+        leaves = [t.to(dtype).clone().requires_grad_(True) if t is not None else None for t in self.ops]
+        ry, rc = oracle_layer(self.mode, *leaves, *self.geom)
+        (ry * self.gy.to(dtype) + rc * self.gc.to(dtype)).sum().backward()
+        return [None if t is None or t.grad is None else t.grad.double() for t in leaves]
+
+    def majorant(self):
+        xa, ca, xb, cb, w, b = self.ops
+        with torch.no_grad():
+            x, c = glue(self.mode, xa, ca, xb, cb)
+            A_x, A_c, A_w, A_b = nconv2d_backward_majorant(x, c, w, b, self.gy, self.gc, *self.geom)
+        return list(glue_adjoint(self.mode, xa, ca, xb, cb, A_x, A_c)) + [A_w, A_b]
+
+    def kappa_ref(self):
+        """Per tensor max_i |err_i| / A_i of the oracle's float32 run against its float64 run."""
+        ref, f32, A = self.grads(), self.grads(torch.float32), self.majorant()
+        return {lab: float(((g - r).abs() / (a + 1e-30)).max())
+                for lab, r, g, a in zip(GRAD_LABELS, ref, f32, A) if r is not None}
+
+
+def _outputs_like(p_ops, mode, geom):
+    with torch.no_grad():
+        return oracle_layer(mode, *p_ops, *geom)
+
+
+def layer_bwd_problem(case):
+    """test_layer_backward's operands (seed 4321, output gradients from seed 99), fp32-rounded."""
+    name, mode, cin, cout, k, pad, stride, dil, groups, *_ = case
+    ops = [r32(t) for t in build_case(case, 4321)]
+    geom = ((stride, stride), (pad, pad), (dil, dil), groups)
+    ry, rc = _outputs_like(ops, mode, geom)
+    g = torch.Generator().manual_seed(99)
+    gy = r32(torch.randn(ry.shape, generator=g, dtype=torch.float64))
+    gc = r32(torch.randn(rc.shape, generator=g, dtype=torch.float64))
+    return BwdProblem(name, mode, ops, gy, gc, geom)
+
+
+def phase_bwd_problem(case):
+    """test_upcat_phase_backward's operands (one generator, seed 23), fp32-rounded."""
+    name, mode, pad, a_shape, b_shape = case
+    g = torch.Generator().manual_seed(23)
+    xa, ca = rand_pair(g, 2, *a_shape, dtype=torch.float64)
+    xb, cb = rand_pair(g, 2, *b_shape, dtype=torch.float64)
+    w = rand_weight(g, 8, 16, 3, 3, torch.float64)
+    b = torch.rand(8, generator=g, dtype=torch.float64) * 0.1
+    ops = [r32(t) for t in (xa, ca, xb, cb, w, b)]
+    geom = ((1, 1), (pad, pad), (1, 1), 1)
+    ry, rc = _outputs_like(ops, mode, geom)
+    gy = r32(torch.randn(ry.shape, generator=g, dtype=torch.float64))
+    gc = r32(torch.randn(rc.shape, generator=g, dtype=torch.float64))
+    return BwdProblem(name, mode, ops, gy, gc, geom)
+
+
+MODULE_SIZES = [(30, 44), (262, 70)]  # 262 rows: the two-row 5x5 weight gradient
+
+
+def module_inputs(H, W):
+    """test_nconv2d_module_train_step's data, confidence and output gradient (float64, unrounded)."""
+    g = torch.Generator().manual_seed(5)
+    x, c = rand_pair(g, 2, 8, H, W, dtype=torch.float64)
+    gy = torch.randn(2, 8, H, W, generator=g, dtype=torch.float64)
+    return x, c, gy
+
+
+def module_bwd_problem(H, W, w, b):
+    """The standalone NConv2d 8 -> 8 5x5 p2 training step, loss sum(y * gy + cout): w, b are the
+    weights and bias the layer ran with (EnforcePos applied)."""
+    x, c, gy = module_inputs(H, W)
+    ops = [r32(t) for t in (x, c, None, None, w.double(), b.double())]
+    gy = r32(gy)
+    return BwdProblem(f"module_{H}x{W}", PLAIN, ops, gy, torch.ones_like(gy), ((1, 1), (2, 2), (1, 1), 1))
+
+
+def module_init_weights():
+    """The weight and bias of NConv2d(8, 8, (5, 5), "softplus", "p") under torch.manual_seed(3) with
+    its EnforcePos hook applied, in fp32 on the CPU (the parameters the module test starts from)."""
+    import nconv_pkg
+    m = nconv_pkg.load()
+    torch.manual_seed(3)
+    layer = m.NConv2d(8, 8, (5, 5), "softplus", "p", padding=(2, 2))
+    return R.softplus_pos(layer.weight.detach()), layer.bias.detach().clone()
+
+
+@functools.lru_cache(maxsize=None)
+def budget(kind, name):
+    """(problem, float64 gradients, majorant) of a LAYER_CASES ("layer") or PHASE_CASES ("phase")
+    entry, computed once and shared (read-only) by the tests that need it."""
+    if kind == "layer":
+        prob = layer_bwd_problem(next(c for c in LAYER_CASES if c[0] == name))
+    else:
+        prob = phase_bwd_problem(next(c for c in PHASE_CASES if c[0] == name))
+    return prob, prob.grads(), prob.majorant()
+
+
+def kappa(label, kref, cin_g, k, bwd_math="fp32"):
+    """The bound's kappa from the reference's own kappa_ref: 4x for another summation order (box,
+    phase and row-pair regroupings, fixed-order partial trees) and the cout * s / y - b recoveries.
+    Input gradients: floored at 2^-22 (a lucky reference run sets no impossible bar) and capped at
+    the a-priori dot-product bound (Cin/groups * K^2 + 8) * 2^-24. Weight and bias gradients sum
+    over every pixel of the batch and have no useful a-priori cap. bf16x3 adds its per-product
+    bound."""
+    kap = 4 * kref
+    if label not in ("g_w", "g_b"):
+        kap = min(max(kap, KAPPA_FLOOR), (cin_g * k * k + 8) * 2.0 ** -24)
+    return kap + (BF16X3_PER_PRODUCT if bwd_math == "bf16x3" else 0.0)
+
+
+def elementwise_excess(got, ref, A, kap):
+    """(worst err / (kappa A + 1e-30), its index, elements compared) of the criterion."""
+    assert got.shape == ref.shape == A.shape, (got.shape, ref.shape, A.shape)
+    ratio = (got - ref).abs() / (kap * A + 1e-30)
+    finite = torch.isfinite(ratio)
+    worst = int(torch.where(finite, ratio, torch.full_like(ratio, float("inf"))).argmax())
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), ratio.shape))
+    return float(ratio.flatten()[worst]), idx, int(finite.sum())
+
+
+def assert_gradients_elementwise(what, problem, got, kappas, bwd_math="fp32", ref=None, A=None):
+    """The element-wise criterion on the six gradients. got: float64 CPU tensors (None where the
+    layer has no such input); kappas: {label: kappa_ref}. Every element is compared. Returns the
+    worst err / (kappa A) per tensor."""
+    ref = problem.grads() if ref is None else ref
+    A = problem.majorant() if A is None else A
+    worst, bad = {}, []
+    for lab, r, a, g in zip(GRAD_LABELS, ref, A, got):
+        if r is None:
+            continue
+        kap = kappa(lab, kappas[lab], problem.cin_g, problem.k, bwd_math)
+        ratio, idx, n = elementwise_excess(g, r, a, kap)
+        assert n == r.numel(), f"{what} {lab}: {r.numel() - n} elements not comparable"
+        worst[lab] = ratio
+        if ratio > 1:
+            pos = f", tile position ({idx[-2] % TILE[0]}, {idx[-1] % TILE[1]})" if lab not in ("g_w", "g_b") else ""
+            bad.append(f"{what} {lab} [{bwd_math}]: err / (kappa A) = {ratio:.3g} at {idx}{pos}; kappa {kap:.3e}, "
+                       f"got {float(g[idx]):.9e}, ref {float(r[idx]):.9e}, A {float(a[idx]):.3e}")
+    print(f"{what} [{bwd_math}] worst err/(kappa A): " + " ".join(f"{k}={v:.3f}" for k, v in worst.items()))
+    assert not bad, "\n".join(bad)
+    return worst
+
+
+def load_kappa():
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bwd_bound_kappa.json")) as fh:
+        return json.load(fh)

@@ -7,10 +7,14 @@ autograd of the same ops, and one whole SETP2_BP_TRAIN training step against the
 Tolerances (normwise, max|gpu - ref| / max|ref| per tensor): 2e-5 for outputs and input gradients,
 1e-4 for weight / bias gradients (fp32 sums over every pixel of the batch); whole training step:
 outputs 1e-4 * |ref| + 1e-3 elementwise, gradients 1e-3 normwise."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
+from dense_cases import CASES, FWD_REL, DenseProblem, case_id
+from nconv_cases import elementwise_excess, load_kappa
 from oracle import nconv_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -23,24 +27,14 @@ def _close(got, ref, what, tol):
     assert err <= tol * scale + 1e-12, f"{what}: max err {err:.3e} (ref max {scale:.3e}, tol {tol})"
 
 
-# kind (0 3x3, 1 1x1, 2 ConvTranspose 4x4 s2), stride, C0, C1 (second source), Cout, H, W, relu, bias
-CASES = [
-    (0, 1, 32, 32, 32, 19, 45, True, True),     # ConvBlock fuse_conv1 on cat(rgb_feat, depth_feat)
-    (0, 1, 64, 64, 64, 12, 40, False, False),   # UpCat conv 128 -> 64 (BatchNorm follows)
-    (0, 1, 1, 0, 32, 13, 33, True, True),       # depth_conv 1 -> 32
-    (0, 1, 64, 0, 64, 9, 70, True, True),       # rgb_conv 64 -> 64
-    (0, 2, 32, 0, 64, 17, 43, False, True),     # encoder 3x3 s2, odd sizes (cropped transposed dgrad)
-    (0, 2, 64, 0, 64, 16, 40, False, True),     # encoder 3x3 s2, even sizes
-    (0, 1, 3, 0, 32, 16, 40, False, True),      # encoder0 3 -> 32
-    (1, 1, 3, 0, 32, 11, 35, False, False),     # encoder0 shortcut 1x1
-    (1, 2, 64, 0, 64, 15, 41, False, False),    # shortcut 1x1 s2, odd sizes
-    (2, 2, 1, 64, 64, 7, 20, False, False),     # Basic2dTrans on cat(depth, features): 65 -> 64
-    (2, 2, 1, 32, 32, 9, 19, False, True),      # 33 -> 32, with bias
-    (0, 1, 32, 0, 1, 14, 37, False, False),     # 3x3 to one channel through the generic tiles
-    (0, 1, 1, 32, 32, 11, 37, True, True),      # 33 input channels, the depth channel first (a chunk
-                                                #   straddling the sources; two weight-gradient n-groups)
-    (0, 2, 33, 0, 64, 13, 29, False, True),     # stride 2, 33 input channels, odd sizes
-]
+@functools.lru_cache(maxsize=None)
+def _dense_budget(i):
+    """Case i's fp32-rounded operands with the float64 reference (pre-activation, output, gradients),
+    the forward bound and the gradient majorants: computed once, shared by the three maths."""
+    prob = DenseProblem(CASES[i])
+    pre, y, grads = prob.run()
+    mask = (pre > 0) if prob.relu else torch.ones_like(pre, dtype=torch.bool)
+    return prob, pre, y, grads, prob.forward_bound(), prob.majorants(mask)
 
 
 @pytest.mark.parametrize("math", ["bf16x9", "fp32", "bf16x6"])
@@ -48,39 +42,42 @@ CASES = [
 def test_dense_conv_fn_forward_backward(nconv_amd, gpu, monkeypatch, math, kind, stride, c0, c1, cout, H, W, relu,
                                         bias):
     """Forward, input and weight gradients under each nconv_dense_math (the split-bf16 weight
-    gradient runs the 3x3 cases of >= 4 input channels)."""
+    gradient runs the 3x3 cases of >= 4 input channels), against float64 of the fp32-rounded
+    operands. The ReLU mask is the reference's: the seeds (dense_cases.SEED_OFFSET) leave no
+    reference pre-activation within the forward bound 1e-6 * (|x| (*) |w| + |b|) of zero, so a
+    forward within its bound decides every element as the reference does. Gradients: normwise as
+    before, and per element |gpu - ref| <= 1e-6 * (|g| (*)^T |w|) for the inputs (the forward's
+    kernels, the forward's figure) and kappa * A for weight and bias, A = wgrad(|x|, |g|) / sum |g|,
+    kappa = 4 x the float32 reference's own (tests/golden/bwd_bound_kappa.json)."""
     D = nconv_amd.dense
     monkeypatch.setattr(D, "MATH", math)
-    g = torch.Generator().manual_seed(kind * 1000 + c0 * 10 + cout + H)
-    B, cin = 2, c0 + c1
-    x0 = torch.randn(B, c0, H, W, generator=g, dtype=torch.float64)
-    x1 = torch.randn(B, c1, H, W, generator=g, dtype=torch.float64) if c1 else None
-    if kind == 2:
-        w = torch.randn(cin, cout, 4, 4, generator=g, dtype=torch.float64) * 0.1
-    else:
-        k = 3 if kind == 0 else 1
-        w = torch.randn(cout, cin, k, k, generator=g, dtype=torch.float64) * 0.1
-    b = torch.randn(cout, generator=g, dtype=torch.float64) if bias else None
+    case = (kind, stride, c0, c1, cout, H, W, relu, bias)
+    prob, pre, yref, gref, fbound, A = _dense_budget(CASES.index(case))
+    if relu:
+        assert not (pre.abs() <= fbound).any(), "a reference pre-activation within the forward bound of 0"
 
-    q = [t.to(gpu, torch.float32).requires_grad_(True) if t is not None else None for t in (x0, x1, w, b)]
+    q = [t.to(gpu, torch.float32).requires_grad_(True) if t is not None else None for t in prob.ops]
     yg = D.conv_fn(q[0], q[2], q[3], kind, stride, relu=relu, x1=q[1])
-    gy = torch.randn(yg.shape, generator=g, dtype=torch.float64)
-    yg.backward(gy.to(gpu, torch.float32))
+    yg.backward(prob.gy.to(gpu, torch.float32))
     torch.cuda.synchronize()
 
-    r = [t.clone().requires_grad_(True) if t is not None else None for t in (x0, x1, w, b)]
-    x = torch.cat([r[0], r[1]], 1) if c1 else r[0]
-    if kind == 2:
-        y = F.conv_transpose2d(x, r[2], r[3], 2, 1)
-    else:
-        y = F.conv2d(x, r[2], r[3], stride, r[2].shape[-1] // 2)
-    if relu:  # the ReLU mask the GPU took (elements within rounding of 0 may differ)
-        y = y * (yg.detach().double().cpu() > 0)
-    y.backward(gy)
-    _close(yg.detach(), y.detach(), "forward", 2e-5)
-    for name, a, ref, tol in zip(("x0", "x1", "weight", "bias"), q, r, (2e-5, 2e-5, 1e-4, 1e-4)):
-        if a is not None:
-            _close(a.grad, ref.grad, f"grad {name}", tol)
+    if relu:
+        assert torch.equal(yg.detach().cpu() > 0, pre > 0), "ReLU decisions differ from the reference's"
+    _close(yg.detach(), yref, "forward", 2e-5)
+    kap = load_kappa()["dense"][case_id(case)]
+    bad = []
+    for name, lab, a, ref, maj, tol in zip(("x0", "x1", "weight", "bias"), ("g_x0", "g_x1", "g_w", "g_b"), q, gref, A,
+                                           (2e-5, 2e-5, 1e-4, 1e-4)):
+        if a is None:
+            continue
+        _close(a.grad, ref, f"grad {name}", tol)
+        k = FWD_REL if lab in ("g_x0", "g_x1") else 4 * kap[lab]
+        ratio, idx, n = elementwise_excess(a.grad.double().cpu(), ref, maj, k)
+        assert n == ref.numel(), f"grad {name}: {ref.numel() - n} elements not comparable"
+        print(f"{case_id(case)} [{math}] grad {name}: worst err / (kappa A) = {ratio:.3f}")
+        if ratio > 1:
+            bad.append(f"grad {name} [{math}]: err / (kappa A) = {ratio:.3g} at {idx}, kappa {k:.3e}")
+    assert not bad, "\n".join(bad)
 
 
 def test_head_fn_forward_backward(nconv_amd, gpu):
@@ -191,21 +188,44 @@ def test_guided_training_step_matches_oracle(nconv_amd, gpu, H, W):
     assert named["rgb_encoder4.encoder.0.weight"].grad is None  # unused in forward (step2.py:46)
 
 
-@pytest.mark.parametrize("B,C,H,W,relu", [(2, 32, 19, 45, True), (3, 64, 8, 10, False), (1, 33, 100, 130, True),
-                                          # the bench's guided batch (4 frames per pair) at decoder sizes
-                                          (4, 32, 352, 1216, True), (4, 128, 44, 152, False)])
-def test_batchnorm_relu_train(nconv_amd, gpu, B, C, H, W, relu):
-    """Training-mode BatchNorm2d (+ ReLU) against nn.BatchNorm2d in float64: output, running-stat
-    update (momentum 0.1, unbiased variance), num_batches_tracked, and the three gradients."""
-    D = nconv_amd.dense
-    g = torch.Generator().manual_seed(B * 100 + C)
-    x = torch.randn(B, C, H, W, generator=g, dtype=torch.float64) * 3 + 1.5
+def _bn_reference(x, C, relu, g):
+    """nn.BatchNorm2d(C) in float64 with seeded affine parameters and running statistics, and its
+    training-mode pre-activation on x."""
     ref_bn = torch.nn.BatchNorm2d(C).double()
     with torch.no_grad():
         ref_bn.weight.uniform_(0.5, 1.5, generator=g)
         ref_bn.bias.uniform_(-0.5, 0.5, generator=g)
         ref_bn.running_mean.uniform_(-1, 1, generator=g)
         ref_bn.running_var.uniform_(0.5, 2, generator=g)
+    return ref_bn
+
+
+def _clear_relu_margin(x, ref_bn, tol):
+    """The ReLU mask is the reference's, so no reference pre-activation may lie within the forward
+    tolerance (tol of max|ref|) of zero: a forward inside its tolerance then decides every element
+    as the reference does. At these sizes no seed gives that, so the few inputs whose pre-activation
+    falls inside the margin are moved by 0.01 sigma of their channel (their pre-activation by
+    >= 5e-3, hundreds of margins; the batch statistics by less than 1e-8 sigma) until none is left.
+    Returns the fp32-exact input and the number of elements moved."""
+    w, b = ref_bn.weight.detach().view(1, -1, 1, 1), ref_bn.bias.detach().view(1, -1, 1, 1)
+    moved = 0
+    for _ in range(8):
+        var, mean = torch.var_mean(x, (0, 2, 3), unbiased=False, keepdim=True)
+        z = (x - mean) / torch.sqrt(var + ref_bn.eps) * w + b
+        near = z.abs() <= 2 * tol * z.clamp_min(0).max()
+        if not near.any():
+            return x, moved
+        moved += int(near.sum())
+        x = torch.where(near, x + 0.01 * torch.sqrt(var), x).float().double()
+    raise AssertionError("pre-activations within the ReLU margin remain")
+
+
+def _bn_relu_train(nconv_amd, gpu, x, C, relu, g):
+    D = nconv_amd.dense
+    ref_bn = _bn_reference(x, C, relu, g)
+    if relu:
+        x, moved = _clear_relu_margin(x, ref_bn, 1e-5)
+        print(f"{moved} of {x.numel()} inputs moved off the ReLU margin")
     bn = torch.nn.BatchNorm2d(C).to(gpu)
     bn.load_state_dict({k: v.float() if v.is_floating_point() else v for k, v in ref_bn.state_dict().items()})
     bn.train()
@@ -213,21 +233,57 @@ def test_batchnorm_relu_train(nconv_amd, gpu, B, C, H, W, relu):
     xg = x.to(gpu, torch.float32).requires_grad_(True)
     y = D.bn_relu(xg, bn, relu)
     xr = x.clone().requires_grad_(True)
-    yr = ref_bn(xr)
-    yr = torch.relu(yr) if relu else yr
-    if relu:  # the ReLU mask the GPU took
-        yr = yr * (y.detach().double().cpu() > 0)
+    pre = ref_bn(xr)
+    yr = torch.relu(pre) if relu else pre
+    if relu:  # the reference's own mask, and the condition that makes it the GPU's
+        margin = 1e-5 * yr.detach().abs().max()
+        assert not (pre.detach().abs() <= margin).any(), "a reference pre-activation within the forward tolerance of 0"
+        assert torch.equal(y.detach().cpu() > 0, pre.detach() > 0), "ReLU decisions differ from the reference's"
     gy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     y.backward(gy.to(gpu, torch.float32))
     yr.backward(gy)
     torch.cuda.synchronize()
-    _close(y.detach(), yr.detach(), "forward", 1e-5)
-    _close(bn.running_mean, ref_bn.running_mean, "running_mean", 1e-5)
-    _close(bn.running_var, ref_bn.running_var, "running_var", 1e-5)
     assert int(bn.num_batches_tracked) == int(ref_bn.num_batches_tracked) == 1
-    _close(xg.grad, xr.grad, "grad x", 1e-4)
-    _close(bn.weight.grad, ref_bn.weight.grad, "grad weight", 1e-4)
-    _close(bn.bias.grad, ref_bn.bias.grad, "grad bias", 1e-4)
+    bad = []  # every figure before the verdict
+    for what, got, ref, tol in (("forward", y.detach(), yr.detach(), 1e-5),
+                                ("running_mean", bn.running_mean, ref_bn.running_mean, 1e-5),
+                                ("running_var", bn.running_var, ref_bn.running_var, 1e-5),
+                                ("grad x", xg.grad, xr.grad, 1e-4),
+                                ("grad weight", bn.weight.grad, ref_bn.weight.grad, 1e-4),
+                                ("grad bias", bn.bias.grad, ref_bn.bias.grad, 1e-4)):
+        err = (got.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
+        print(f"{what}: max err / max|ref| = {err:.3e} (tol {tol})")
+        try:
+            _close(got, ref, what, tol)
+        except AssertionError as e:
+            bad.append(str(e))
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("B,C,H,W,relu", [(2, 32, 19, 45, True), (3, 64, 8, 10, False), (1, 33, 100, 130, True),
+                                          # the bench's guided batch (4 frames per pair) at decoder sizes
+                                          (4, 32, 352, 1216, True), (4, 128, 44, 152, False)])
+def test_batchnorm_relu_train(nconv_amd, gpu, B, C, H, W, relu):
+    """Training-mode BatchNorm2d (+ ReLU) against nn.BatchNorm2d in float64 on the fp32-rounded
+    input: output, running-stat update (momentum 0.1, unbiased variance), num_batches_tracked, and
+    the three gradients. The ReLU mask is the reference's (asserted equal to the GPU's)."""
+    g = torch.Generator().manual_seed(B * 100 + C)
+    x = (torch.randn(B, C, H, W, generator=g, dtype=torch.float64) * 3 + 1.5).float().double()
+    _bn_relu_train(nconv_amd, gpu, x, C, relu, g)
+
+
+def test_batchnorm_relu_train_offset_mean(nconv_amd, gpu):
+    """The depth channel's regime: a mean of 40 under a spread of 0.05, where a variance
+    formed as E[x^2] - E[x]^2 in fp32 has no correct digit left. Same tolerances, relative to
+    max|ref| of each tensor.
+
+    This case found the one-word batch mean: the forward was off by 2.158e-5 of max|ref| (1.210e-04
+    at 5.607) against its 1e-5, a few ulp(40) of the mean times invstd ~ 20 and gamma <= 1.5. The
+    kernels now carry the mean as two fp32 words (csrc/batchnorm.hip)."""
+    B, C, H, W = 2, 32, 19, 45
+    g = torch.Generator().manual_seed(4040)
+    x = (torch.randn(B, C, H, W, generator=g, dtype=torch.float64) * 0.05 + 40).float().double()
+    _bn_relu_train(nconv_amd, gpu, x, C, True, g)
 
 
 @pytest.mark.parametrize("B,C,H,W,relu", [(2, 32, 19, 45, True), (3, 64, 8, 10, False), (1, 5, 3, 7, True)])

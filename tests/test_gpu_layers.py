@@ -3,32 +3,21 @@ oracle (tests/nconv_cases.oracle_layer = reference glue + models/step1.py:116-14
 
 Tolerances (written here, from BASELINE.json's north star and SURVEY.md 8(c)):
   forward  : elementwise |gpu - ref| <= 1e-4 * |ref| + 1e-5          (fp32 kernel vs fp64 oracle)
-  backward : max|gpu - ref| / max|ref| <= 1e-3 per gradient tensor     
+  backward : max|gpu - ref| / max|ref| <= 1e-3 per gradient tensor     (SURVEY.md 8(c)), and per element
+             |gpu - ref| <= kappa * A + 1e-30 against the float64 oracle of the fp32-rounded operands:
+             A the gradient majorant (nconv_cases.nconv2d_backward_majorant), kappa 4x what the
+             reference's own float32 run costs (tests/golden/bwd_bound_kappa.json, nconv_cases.kappa)
 """
 import pytest
 import torch
 
-from nconv_cases import LAYER_CASES, THRESH, oracle_layer, rand_pair, rand_weight
+import nconv_cases as NC
+from nconv_cases import LAYER_CASES, PHASE_CASES, THRESH, oracle_layer, rand_pair, rand_weight
 
 pytestmark = pytest.mark.gpu
 
 
-def _build(case, seed):
-    name, mode, cin, cout, k, pad, stride, dil, groups, a_shape, b_shape = case
-    g = torch.Generator().manual_seed(seed)
-    xa, ca = rand_pair(g, 2, *a_shape, dtype=torch.float64)
-    if mode == THRESH:
-        xa = xa * (torch.rand(xa.shape, generator=g, dtype=torch.float64) < 0.3)
-        ca = None
-    if name.endswith("_ties"):  # small integer values and a 3-level confidence: many exact ties
-        xa = torch.randint(0, 3, xa.shape, generator=g).double()
-        ca = torch.randint(0, 3, ca.shape, generator=g).double() * 0.5
-    xb = cb = None
-    if b_shape is not None:
-        xb, cb = rand_pair(g, 2, *b_shape, dtype=torch.float64)
-    w = rand_weight(g, cout, cin // groups, k, k, torch.float64)
-    b = torch.rand(cout, generator=g, dtype=torch.float64) * 0.1
-    return xa, ca, xb, cb, w, b
+_build = NC.build_case
 
 
 def _spec(nconv_amd, case):
@@ -84,14 +73,11 @@ def bwd_math(request, nconv_amd, monkeypatch):
 
 @pytest.mark.parametrize("case", LAYER_CASES, ids=[c[0] for c in LAYER_CASES])
 def test_layer_backward(nconv_amd, gpu, case, bwd_math):
-    xa, ca, xb, cb, w, b = _build(case, 4321)
     name, mode, cin, cout, k, pad, stride, dil, groups, *_ = case
-    leaves = [t.clone().requires_grad_(True) if t is not None else None for t in (xa, ca, xb, cb, w, b)]
-    ry, rc = oracle_layer(mode, *leaves, (stride, stride), (pad, pad), (dil, dil), groups)
-    g = torch.Generator().manual_seed(99)
-    gy = torch.randn(ry.shape, generator=g, dtype=torch.float64)
-    gc = torch.randn(rc.shape, generator=g, dtype=torch.float64)
-    (ry * gy + rc * gc).sum().backward()
+    # fp32-rounded operands, the float64 oracle's gradients and their majorant: computed once per case
+    prob, refs, A = NC.budget("layer", name)
+    xa, ca, xb, cb, w, b = prob.ops
+    gy, gc = prob.gy, prob.gc
 
     gl = [_gpu(t, gpu, grad=True) for t in (xa, ca, xb, cb, w, b)]
     wsum = _wsum(nconv_amd, gl[4])
@@ -107,16 +93,16 @@ def test_layer_backward(nconv_amd, gpu, case, bwd_math):
     y, c = nconv_amd.nconv_layer(_spec(nconv_amd, case), *gl[:4], gl[4], gl[5], wsum)
     (y * gy.to(gpu, torch.float32) + c * gc.to(gpu, torch.float32)).sum().backward()
     torch.cuda.synchronize()
-    labels = ("g_xa", "g_ca", "g_xb", "g_cb", "g_w", "g_b")
-    for lab, ref_leaf, got_leaf in zip(labels, leaves, gl):
-        if ref_leaf is None or ref_leaf.grad is None:
+    got = [None if t is None or t.grad is None else t.grad.double().cpu() for t in gl]
+    for lab, ref, g in zip(NC.GRAD_LABELS, refs, got):
+        assert (ref is None) == (g is None), lab
+        if ref is None:
             continue
-        ref = ref_leaf.grad
-        got = got_leaf.grad.double().cpu()
-        rel = ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
+        rel = ((g - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
         assert rel <= 1e-3, f"{name} {lab} [{bwd_math}]: normwise rel err {rel:.3e}"
         if lab == "g_w":
             print(f"{name} g_w [{bwd_math}]: normwise rel err {rel:.2e}")
+    NC.assert_gradients_elementwise(name, prob, got, NC.load_kappa()["layer"][name], bwd_math, refs, A)
 
 
 @pytest.mark.parametrize("case", [c for c in LAYER_CASES if c[0] in ("nconv2_plain", "down_pool_odd",
@@ -182,7 +168,7 @@ def test_bwd_accumulate_flag(nconv_amd, gpu, case, bwd_math):
         assert torch.equal(gws[k], gw0) and torch.equal(gbs[k], gb0), "deferred reduction differs"
 
 
-@pytest.mark.parametrize("H,W", [(30, 44), (262, 70)])  # 262 rows: the two-row 5x5 weight gradient
+@pytest.mark.parametrize("H,W", NC.MODULE_SIZES)  # 262 rows: the two-row 5x5 weight gradient
 def test_nconv2d_module_train_step(nconv_amd, gpu, H, W):
     """Standalone NConv2d (the reference's layer API): EnforcePos pre-hook + forward + backward."""
     from oracle import nconv_ref as R
@@ -207,6 +193,12 @@ def test_nconv2d_module_train_step(nconv_amd, gpu, H, W):
     for got, ref in ((xg.grad, xr.grad), (cg.grad, cr.grad), (layer.weight.grad, wr.grad), (layer.bias.grad, br.grad)):
         rel = ((got.double().cpu() - ref).abs().max() / ref.abs().max()).item()
         assert rel <= 1e-3, rel
+    # element-wise, against float64 of the operands the layer ran with: the fp32 data and confidence,
+    # the weight its EnforcePos hook left in place
+    prob = NC.module_bwd_problem(H, W, layer.weight.detach().cpu(), layer.bias.detach().cpu())
+    got = [t.double().cpu() if t is not None else None
+           for t in (xg.grad, cg.grad, None, None, layer.weight.grad, layer.bias.grad)]
+    NC.assert_gradients_elementwise(prob.name, prob, got, NC.load_kappa()["module"][f"{H}x{W}"])
 
 
 def test_fwd_head_negative_weights_sign_of_zero(nconv_amd, gpu):
@@ -338,19 +330,6 @@ def test_fwd_head_matches_unfused(nconv_amd, gpu, shape, monkeypatch):
     assert torch.equal(pc1, torch.nn.functional.max_pool2d(c1f, 2, 2))
 
 
-# Exact-2x UPCAT layers on the phase path (nconv_layer.wphase, nconv_fwd_phase.hip): both channel
-# orders, paddings 0 / 1 / 2 (both phase parities), ragged widths, tiles cut by the image edge.
-# (name, mode, pad, a-shape, b-shape)
-PHASE_CASES = [
-    ("skip_p1", 3, 1, (8, 24, 70), (8, 12, 35)),
-    ("skip_p1_w4", 3, 1, (8, 26, 72), (8, 13, 36)),
-    ("skip_p0", 3, 0, (8, 20, 64), (8, 10, 32)),
-    ("skip_p2", 3, 2, (8, 18, 46), (8, 9, 23)),
-    ("up_p0", 4, 0, (8, 34, 72), (8, 17, 36)),
-    ("up_p1", 4, 1, (8, 36, 66), (8, 18, 33)),
-]
-
-
 @pytest.mark.parametrize("case", PHASE_CASES, ids=[c[0] for c in PHASE_CASES])
 def test_upcat_phase_forward(nconv_amd, gpu, case):
     """The phase path (upsampled half at native resolution with summed fp32 weights) against the
@@ -393,16 +372,9 @@ def test_upcat_phase_backward(nconv_amd, gpu, case):
     SURVEY 8(c)), with nconv_plan naming the phase kernel; padding 0 / 1 / 2 and both channel orders
     put the low pixels' 4x4 windows at every alignment against the image edge."""
     name, mode, pad, a_shape, b_shape = case
-    g = torch.Generator().manual_seed(23)
-    xa, ca = rand_pair(g, 2, *a_shape, dtype=torch.float64)
-    xb, cb = rand_pair(g, 2, *b_shape, dtype=torch.float64)
-    w = rand_weight(g, 8, 16, 3, 3, torch.float64)
-    b = torch.rand(8, generator=g, dtype=torch.float64) * 0.1
-    leaves = [t.clone().requires_grad_(True) for t in (xa, ca, xb, cb, w, b)]
-    ry, rc = oracle_layer(mode, *leaves, (1, 1), (pad, pad))
-    gy = torch.randn(ry.shape, generator=g, dtype=torch.float64)
-    gc = torch.randn(rc.shape, generator=g, dtype=torch.float64)
-    (ry * gy + rc * gc).sum().backward()
+    prob, refs, A = NC.budget("phase", name)  # fp32-rounded operands, float64 gradients, majorant
+    xa, ca, xb, cb, w, b = prob.ops
+    gy, gc = prob.gy, prob.gc
     spec = nconv_amd.LayerSpec(16, 8, (3, 3), (1, 1), (pad, pad), mode=mode)
     gl = [_gpu(t, gpu, grad=True) for t in (xa, ca, xb, cb, w, b)]
     wsum = _wsum(nconv_amd, gl[4])
@@ -410,7 +382,8 @@ def test_upcat_phase_backward(nconv_amd, gpu, case):
     y, c = nconv_amd.nconv_layer(spec, *gl[:4], gl[4], gl[5], wsum)
     (y * gy.to(gpu, torch.float32) + c * gc.to(gpu, torch.float32)).sum().backward()
     torch.cuda.synchronize()
-    for lab, ref_leaf, got_leaf in zip(("g_xa", "g_ca", "g_xb", "g_cb", "g_w", "g_b"), leaves, gl):
-        ref, got = ref_leaf.grad, got_leaf.grad.double().cpu()
-        rel = ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
+    got = [t.grad.double().cpu() for t in gl]
+    for lab, ref, g in zip(NC.GRAD_LABELS, refs, got):
+        rel = ((g - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
         assert rel <= 1e-3, f"{name} {lab}: normwise rel err {rel:.3e}"
+    NC.assert_gradients_elementwise(name, prob, got, NC.load_kappa()["phase"][name], "fp32", refs, A)
