@@ -27,6 +27,8 @@ gradient_x = _m.train.gradient_x
 gradient_y = _m.train.gradient_y
 get_optimizer = _m.train.get_optimizer
 save_checkpoint = _m.train.save_checkpoint
+DepthMetrics = _m.metrics.DepthMetrics
+depth_metric_sums = _m.metrics.depth_metric_sums
 
 
 def save_depth(depth_data, path):
@@ -61,3 +63,36 @@ def get_performance_multi_resolution(model, val_loader, device_str, use_gradient
         est, _ = model(rgb, depth, rgb, depth)
         losses.append(calculate_loss_multi_resolution(est, gt, use_gradient_loss).item())
     return sum(losses) / len(losses)
+
+
+def get_metrics(model, val_loader, device_str, unit_m=1.0, **bounds):
+    """Depth-completion figures (nconv_amd.metrics.DepthMetrics.compute: MAE, RMSE, iMAE, iRMSE, REL,
+    delta < 1.25^k, ...) of a step-1 model over every image of every batch; the loop of
+    get_performance with one fused metrics call per batch and one synchronisation at the end.
+    bounds: gt_min, gt_max, clamp=(lo, hi); unit_m: metres per unit of the depth tensors."""
+    device = torch.device(device_str if device_str == "cuda" and torch.cuda.is_available() else "cpu")
+    model.to(device)
+    model.eval()
+    metrics = DepthMetrics(device=device, **bounds)
+    with torch.no_grad():
+        for data in val_loader:
+            depth, gt = data["depth"].to(device), data["gt"].to(device)
+            metrics.update(model(depth), gt)
+    return metrics.compute(unit_m)
+
+
+def get_metrics_multi_resolution(model, val_loader, device_str, unit_m=1.0, **bounds):
+    """get_metrics for a guided model: the call of get_performance_multi_resolution, the finest scale
+    (est[3]) scored against gt."""
+    device = torch.device(device_str if device_str == "cuda" and torch.cuda.is_available() else "cpu")
+    model.to(device)
+    metrics = DepthMetrics(device=device, **bounds)
+    with torch.no_grad():
+        for data in val_loader:
+            rgb, depth, gt = data["rgb"].to(device), data["depth"].to(device), data["gt"].to(device)
+            est, _ = model(rgb, depth, rgb, depth)
+            fine, gt = est[3], gt[0:1]  # the model returns element [0] of the batch, as the loss scores it
+            if fine.shape[-2:] != gt.shape[-2:]:
+                fine = F.interpolate(fine, size=gt.shape[-2:], mode="bilinear", align_corners=False)
+            metrics.update(fine, gt)
+    return metrics.compute(unit_m)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NCONV_ABI_VERSION 23
+#define NCONV_ABI_VERSION 24
 
 /* How a layer's input (data x, confidence c) is produced from its source tensors. These are the
  * DNET glue ops fused into the layer's load stage (models/step1.py:53,61-90). */
@@ -514,6 +514,31 @@ int nconv_depth_loss_fwd(const float* r, long long r_image_stride, long long r_r
 int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          const float* gloss, const void* workspace, size_t workspace_bytes, float* g, void* stream);
+
+/* Depth-completion evaluation figures on B (H, W) planes, as twelve raw sums per image. The
+ * reference reports only its validation loss (utils.py:18-40); the KITTI (MAE, RMSE, iMAE, iRMSE)
+ * and NYU (REL, squared REL, RMSE(log), delta < 1.25^k) figures a user compares with published
+ * numbers are ~40 PyTorch elementwise / reduction launches per frame and one .item() per figure.
+ * This replaces them with two launches and no host synchronisation. pred and gt are fp32 with
+ * image / row strides in elements (pred may be a cropped view whose first element is not 16-byte
+ * aligned). A bound of 0 is absent. A pixel is valid iff gt > 0, gt >= gt_min and gt <= gt_max;
+ * p = pred clamped into [clamp_lo, clamp_hi], g = gt, e = p - g; a valid pixel is positive iff
+ * p > 0 (a NaN prediction at a valid pixel is not positive and makes sums 2-5 NaN). Per image:
+ *    0  n_valid                  4  sum |e| / g               8  sum (ln p - ln g)^2
+ *    1  n_pos                    5  sum e^2 / g               9  #{max(p/g, g/p) < 1.25}
+ *    2  sum |e|                  6  sum |1/p - 1/g|          10  #{max(p/g, g/p) < 1.5625}
+ *    3  sum e^2                  7  sum (1/p - 1/g)^2        11  #{max(p/g, g/p) < 1.953125}
+ * sums 2-5 over the valid pixels, 6-11 over the positive ones. sums (B x 12 doubles, OVERWRITTEN;
+ * NULL: skip) receives each image's row; accum (12 doubles; NULL: skip) is then increased by the
+ * rows of images 0 .. B-1 in that order (a running total over calls). Per-pixel terms in fp32 (IEEE
+ * division, logf), fp32 partials of 16 x 64 pixel tiles, tiles and images combined in double in a
+ * fixed order: deterministic (no atomics), counts exact. workspace must be 8-byte aligned. */
+#define NCONV_DEPTH_METRICS_SUMS 12
+size_t nconv_depth_metrics_workspace_bytes(int B, int H, int W);
+int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p_row_stride, const float* gt,
+                        long long g_image_stride, long long g_row_stride, int B, int H, int W, float gt_min,
+                        float gt_max, float clamp_lo, float clamp_hi, double* sums, double* accum, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,10 +13,11 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NCONV_LIB: an alternative build of the same library (kernel-tuning experiments)
 LIB_PATH = os.environ.get("NCONV_LIB") or os.path.join(_HERE, "libnconv.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 BWD_ACCUMULATE = 1
 BWD_DEFER_REDUCE = 2
 BWD_SEPARATE = 4  # accepted and ignored since ABI 21 (include/nconv.h)
+DEPTH_METRICS_SUMS = 12  # NCONV_DEPTH_METRICS_SUMS
 
 # enum nconv_load_mode
 PLAIN, THRESH, POOL2, UPCAT_SKIP_FIRST, UPCAT_UP_FIRST = 0, 1, 2, 3, 4
@@ -68,6 +69,8 @@ EXPORTED = (
     "nconv_depth_loss_workspace_bytes",
     "nconv_depth_loss_fwd",
     "nconv_depth_loss_bwd",
+    "nconv_depth_metrics_workspace_bytes",
+    "nconv_depth_metrics",
 )
 
 
@@ -209,6 +212,11 @@ def _declare(lib):
     lib.nconv_depth_loss_fwd.argtypes = [P, L, L, P, L, L, I, I, I, I, P, P, ctypes.c_size_t, P]
     lib.nconv_depth_loss_bwd.restype = I
     lib.nconv_depth_loss_bwd.argtypes = [P, L, L, P, L, L, I, I, I, I, P, P, ctypes.c_size_t, P, P]
+    F = ctypes.c_float
+    lib.nconv_depth_metrics_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_depth_metrics_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_depth_metrics.restype = I
+    lib.nconv_depth_metrics.argtypes = [P, L, L, P, L, L, I, I, I, F, F, F, F, P, P, P, ctypes.c_size_t, P]
 
 
 def lib():

@@ -1,0 +1,161 @@
+// metrics.hip — the depth-completion evaluation figures (KITTI: MAE, RMSE, iMAE, iRMSE; NYU: REL,
+// squared REL, RMSE(log), delta < 1.25^k) as twelve raw sums per image, in two kernels.
+//
+//   valid   g > 0, g >= gt_min, g <= gt_max (a bound of 0 is absent)
+//   p       the prediction clamped into [clamp_lo, clamp_hi] (a bound of 0 is absent; a NaN stays NaN)
+//   e       p - g;  positive = valid and p > 0 (the inverse, log and delta terms)
+//   sums    0 n_valid  1 n_pos  2 sum|e|  3 sum e^2  4 sum|e|/g  5 sum e^2/g  6 sum|1/p - 1/g|
+//           7 sum(1/p - 1/g)^2  8 sum(ln p - ln g)^2  9-11 #{max(p/g, g/p) < 1.25, 1.25^2, 1.25^3}
+//
+// In PyTorch these are ~40 elementwise / reduction launches per frame; here, on the loss's 16 x 64
+// pixel tiles (four consecutive pixels of a row per thread, one 128-bit load per operand where its
+// base and strides are 16-byte aligned, four range-checked dword loads otherwise):
+//   metrics_partials  one workgroup per tile of one image: the per-pixel terms in fp32 (IEEE division,
+//                     logf, no contraction), twelve fp32 tile partials (counts <= 1024 are exact)
+//   metrics_finalize  one block of sixteen waves: a wave per image sums its tiles in a fixed order in
+//                     double -> sums[b][0..11]; then accum[k] += image 0, 1, .. B-1 in that order
+// Deterministic (no atomics), no host synchronisation, 2 x 4 bytes read per pixel.
+#include "nconv_internal.h"
+
+namespace nconv {
+
+constexpr int kMT = 256;
+constexpr int kFT = 1024;  // finalize: sixteen waves, one image each at a time
+constexpr int kMH = 16, kMW = 64;  // pixel tile of one workgroup (4 consecutive pixels per thread)
+constexpr int kNS = NCONV_DEPTH_METRICS_SUMS;
+
+static int metrics_tiles_per_image(int H, int W) { return ((H + kMH - 1) / kMH) * ((W + kMW - 1) / kMW); }
+
+// Four consecutive pixels (row i, columns j .. j+3) of a plane through its buffer resource; pixels
+// outside the plane read 0 (an invalid target). off = the byte offset of (i, j).
+__device__ __forceinline__ f4 metrics_load4(__amdgpu_buffer_rsrc_t r, bool vec, bool row_in, int j, int W,
+                                            unsigned off) {
+    constexpr unsigned OOB = 0x80000000u;
+    if (vec && (!row_in || j + 3 < W))
+        return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, row_in ? off : OOB, 0, 0));
+    f4 v;
+    v.x = ld_f32(r, row_in && j < W ? off : OOB);
+    v.y = ld_f32(r, row_in && j + 1 < W ? off + 4u : OOB);
+    v.z = ld_f32(r, row_in && j + 2 < W ? off + 8u : OOB);
+    v.w = ld_f32(r, row_in && j + 3 < W ? off + 12u : OOB);
+    return v;
+}
+
+// one pixel's terms added to the thread's twelve sums
+__device__ __forceinline__ void metrics_pixel(float pr, float g, const MetricsArgs& a, float (&s)[kNS]) {
+#pragma clang fp contract(off)
+    const bool valid = g > 0.f && g >= a.g_lo && g <= a.g_hi;
+    float p = pr;  // comparisons, not fminf / fmaxf: a NaN prediction stays NaN
+    p = p < a.c_lo ? a.c_lo : p;
+    p = p > a.c_hi ? a.c_hi : p;
+    const bool pos = valid && p > 0.f;
+    const float e = p - g, ae = fabsf(e), e2 = e * e;
+    const float d = 1.f / p - 1.f / g;
+    const float l = logf(p) - logf(g);
+    const float ratio = fmaxf(p / g, g / p);
+    s[0] += valid ? 1.f : 0.f;
+    s[1] += pos ? 1.f : 0.f;
+    s[2] += valid ? ae : 0.f;
+    s[3] += valid ? e2 : 0.f;
+    s[4] += valid ? ae / g : 0.f;
+    s[5] += valid ? e2 / g : 0.f;
+    s[6] += pos ? fabsf(d) : 0.f;
+    s[7] += pos ? d * d : 0.f;
+    s[8] += pos ? l * l : 0.f;
+    s[9] += pos && ratio < 1.25f ? 1.f : 0.f;
+    s[10] += pos && ratio < 1.5625f ? 1.f : 0.f;
+    s[11] += pos && ratio < 1.953125f ? 1.f : 0.f;
+}
+
+// one workgroup per tile; part[tile][0..11], tiles of image b at b * tiles-per-image (a fixed order)
+__global__ __launch_bounds__(kMT) void metrics_partials(MetricsArgs a, float* __restrict__ part) {
+    __shared__ float red[kMT / 64][kNS];
+    const int ntw = (a.W + kMW - 1) / kMW, nth = (a.H + kMH - 1) / kMH;
+    const int b = blockIdx.x / (ntw * nth), t = blockIdx.x - b * ntw * nth;
+    const int i = (t / ntw) * kMH + (threadIdx.x >> 4), j = (t % ntw) * kMW + (threadIdx.x & 15) * 4;
+    const float* pp = a.p + (long long)b * a.pbs;
+    const float* gp = a.g + (long long)b * a.gbs;
+    const __amdgpu_buffer_rsrc_t rp = plane_rsrc(pp, (int)(((long long)(a.H - 1) * a.prs + a.W) * 4));
+    const __amdgpu_buffer_rsrc_t rg = plane_rsrc(gp, (int)(((long long)(a.H - 1) * a.grs + a.W) * 4));
+    const bool row_in = i < a.H;
+    const f4 pv = metrics_load4(rp, a.p_vec != 0, row_in, j, a.W, (unsigned)((long long)i * a.prs + j) * 4u);
+    const f4 gv = metrics_load4(rg, a.g_vec != 0, row_in, j, a.W, (unsigned)((long long)i * a.grs + j) * 4u);
+    float s[kNS];
+#pragma unroll
+    for (int k = 0; k < kNS; ++k) s[k] = 0.f;
+    metrics_pixel(pv.x, gv.x, a, s);
+    metrics_pixel(pv.y, gv.y, a, s);
+    metrics_pixel(pv.z, gv.z, a, s);
+    metrics_pixel(pv.w, gv.w, a, s);
+#pragma unroll
+    for (int k = 0; k < kNS; ++k)
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kNS; ++k) red[w][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kNS) {
+        const int k = threadIdx.x;
+        part[(size_t)blockIdx.x * kNS + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    }
+}
+
+// One block. Wave w reduces images w, w + 16, ..: lane l adds tiles l, l + 64, .. in order (double),
+// then the xor tree over the lanes; the image's row goes to img (workspace) and to sums. After the
+// barrier thread k adds img[0..B)[k] in order into accum[k].
+__global__ __launch_bounds__(kFT) void metrics_finalize(const float* __restrict__ part, int B, int tiles,
+                                                         double* __restrict__ img, double* __restrict__ sums,
+                                                         double* __restrict__ accum) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int b = w; b < B; b += kFT / 64) {
+        const float* pb = part + (size_t)b * tiles * kNS;
+        double s[kNS];
+#pragma unroll
+        for (int k = 0; k < kNS; ++k) s[k] = 0.0;
+        for (int t = lane; t < tiles; t += 64) {
+#pragma unroll
+            for (int k = 0; k < kNS; ++k) s[k] += (double)pb[(size_t)t * kNS + k];
+        }
+#pragma unroll
+        for (int k = 0; k < kNS; ++k)
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+        double mine = 0.0;  // lane k keeps sum k
+#pragma unroll
+        for (int k = 0; k < kNS; ++k) mine = lane == k ? s[k] : mine;
+        if (lane < kNS) {
+            img[(size_t)b * kNS + lane] = mine;
+            if (sums) sums[(size_t)b * kNS + lane] = mine;
+        }
+    }
+    if (!accum) return;
+    __syncthreads();  // img rows written by this block's waves
+    if (threadIdx.x < kNS) {
+        double acc = accum[threadIdx.x];
+        for (int b = 0; b < B; ++b) acc += img[(size_t)b * kNS + threadIdx.x];
+        accum[threadIdx.x] = acc;
+    }
+}
+
+size_t metrics_workspace_bytes(int B, int H, int W) {
+    return (size_t)B * kNS * sizeof(double) + (size_t)B * metrics_tiles_per_image(H, W) * kNS * sizeof(float);
+}
+
+int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, hipStream_t st, const char** why) {
+    const int tiles = metrics_tiles_per_image(a.H, a.W);
+    double* img = (double*)ws;
+    float* part = (float*)(img + (size_t)a.B * kNS);
+    hipLaunchKernelGGL(metrics_partials, dim3(a.B * tiles), dim3(kMT), 0, st, a, part);
+    hipLaunchKernelGGL(metrics_finalize, dim3(1), dim3(kFT), 0, st, part, a.B, tiles, img, sums, accum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *why = hipGetErrorString(e);
+        return -5;
+    }
+    return 0;
+}
+
+}  // namespace nconv

@@ -631,4 +631,44 @@ int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_r
     return rc ? fail(rc, fn, why) : 0;
 }
 
+size_t nconv_depth_metrics_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 30)) return 0;
+    return nconv::metrics_workspace_bytes(B, H, W);
+}
+
+int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p_row_stride, const float* gt,
+                        long long g_image_stride, long long g_row_stride, int B, int H, int W, float gt_min,
+                        float gt_max, float clamp_lo, float clamp_hi, double* sums, double* accum, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_depth_metrics";
+    if (!pred || !gt) return fail(-22, fn, "null plane");
+    if (!sums && !accum) return fail(-22, fn, "null sums and accum");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
+    if (p_row_stride < W || g_row_stride < W) return fail(-22, fn, "row stride smaller than W");
+    // a plane's byte offsets are 32-bit (buffer loads); the image offsets are 64-bit
+    if (p_row_stride >= (1LL << 29) / H || g_row_stride >= (1LL << 29) / H) return fail(-22, fn, "plane too large");
+    if (B > 1 && (p_image_stride < H * p_row_stride || g_image_stride < H * g_row_stride))
+        return fail(-22, fn, "image stride smaller than H * row stride");
+    if (!(gt_min >= 0.f) || !(gt_max >= 0.f) || !(clamp_lo >= 0.f) || !(clamp_hi >= 0.f))
+        return fail(-22, fn, "negative or NaN bound");
+    if (gt_min > 0.f && gt_max > 0.f && gt_min > gt_max) return fail(-22, fn, "gt_min > gt_max");
+    if (clamp_lo > 0.f && clamp_hi > 0.f && clamp_lo > clamp_hi) return fail(-22, fn, "clamp_lo > clamp_hi");
+    if (!workspace || workspace_bytes < nconv::metrics_workspace_bytes(B, H, W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8 || (size_t)sums % 8 || (size_t)accum % 8)
+        return fail(-22, fn, "workspace / sums / accum not 8-byte aligned");
+    auto vec = [&](const float* q, long long bs, long long rs) {
+        return (size_t)q % 16 == 0 && rs % 4 == 0 && (B == 1 || bs % 4 == 0);
+    };
+    const float inf = __builtin_inff();
+    const nconv::MetricsArgs a{pred, gt, B > 1 ? p_image_stride : 0, p_row_stride, B > 1 ? g_image_stride : 0,
+                               g_row_stride, B, H, W, vec(pred, p_image_stride, p_row_stride),
+                               vec(gt, g_image_stride, g_row_stride), gt_min, gt_max > 0.f ? gt_max : inf,
+                               clamp_lo > 0.f ? clamp_lo : -inf, clamp_hi > 0.f ? clamp_hi : inf};
+    const char* why = nullptr;
+    int rc = nconv::launch_metrics(a, sums, accum, workspace, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

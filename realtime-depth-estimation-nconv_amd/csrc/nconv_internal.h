@@ -200,4 +200,18 @@ int launch_loss_fwd(const LossArgs& a, int grad_loss, float* loss, float* ws, hi
 int launch_loss_bwd(const LossArgs& a, int grad_loss, const float* gout, const float* ws, float* g, hipStream_t st,
                     const char** why);
 
+// Evaluation metrics (the twelve raw sums of nconv_depth_metrics) on B planes.
+struct MetricsArgs {
+    const float* p;
+    const float* g;
+    long long pbs, prs;  // image / row strides of the prediction (elements)
+    long long gbs, grs;  // ... of the target
+    int B, H, W;
+    int p_vec, g_vec;   // the operand's image bases and rows are 16-byte aligned: 128-bit loads
+    float g_lo, g_hi;   // validity window of the target (absent bounds: 0, +inf)
+    float c_lo, c_hi;   // clamp window of the prediction (absent bounds: -inf, +inf)
+};
+size_t metrics_workspace_bytes(int B, int H, int W);
+int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, hipStream_t st, const char** why);
+
 }  // namespace nconv
