@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NCONV_ABI_VERSION 24
+#define NCONV_ABI_VERSION 25
 
 /* How a layer's input (data x, confidence c) is produced from its source tensors. These are the
  * DNET glue ops fused into the layer's load stage (models/step1.py:53,61-90). */
@@ -539,6 +539,57 @@ int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p
                         long long g_image_stride, long long g_row_stride, int B, int H, int W, float gt_min,
                         float gt_max, float clamp_lo, float clamp_hi, double* sums, double* accum, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* Raw sensor frames -> the network's fp32 tensors, in one launch per batch (the reference decodes on
+ * the host: torch.FloatTensor(cv2.imread(..)).permute(2, 0, 1) and imread(..) / 256.0,
+ * dataset/kittiloader.py:62-79, and ships fp32 across the link: 20 bytes per pixel for rgb + depth +
+ * gt against 7 as stored). Every source is a strided view given by its base pointer, image stride
+ * and row stride in BYTES, so a crop is a pointer offset plus strides.
+ *   rgb    uint8, interleaved 3-channel (B, h, w, 3); any byte alignment, row stride >= 3 w
+ *          -> rgb_out fp32 (B, 3, h, w) contiguous, exactly float(byte); reverse != 0 writes the
+ *          channels in reverse order (RGB source -> BGR planes, cv2.imread's order). NULL: no RGB.
+ *   plane  up to two single-channel (B, h, w) planes (sparse depth, ground truth), each with its
+ *          own dtype, right shift (integers only, 0..15) and fp32 scale
+ *          -> out fp32 (B, 1, h, w) contiguous = float(v >> shift) * scale; F32: v * scale (one
+ *          fp32 multiply). A 16-bit KITTI PNG in metres: U16, shift 0, scale 1/256; as the
+ *          reference's 8-bit imread sees it: U16, shift 8, scale 1/256. src NULL: absent.
+ *          U16 / F32 sources must be aligned to their element (base and strides).
+ * No byte outside a view's extent [base, base + (B-1) image_stride + (h-1) row_stride + w * element)
+ * is read. Wide loads where base and strides are 4-byte aligned (F32: 16-byte), element-wide
+ * range-checked loads otherwise. One kernel, no workspace. */
+enum nconv_frame_dtype { NCONV_FRAME_U8 = 0, NCONV_FRAME_U16 = 1, NCONV_FRAME_F32 = 2 };
+
+typedef struct nconv_frame_plane {
+    const void* src;        /* NULL: absent                                                  */
+    long long image_stride; /* bytes (ignored when B == 1)                                   */
+    long long row_stride;   /* bytes, >= w * element size                                    */
+    int dtype;              /* enum nconv_frame_dtype                                        */
+    int shift;              /* 0..15; 0 for F32                                              */
+    float scale;
+    float* out;             /* (B, 1, h, w) contiguous fp32                                  */
+} nconv_frame_plane;
+
+/* (the struct tag shares its name with the entry point: spell the type `struct nconv_frame_ingest`
+ * or nconv_frame_ingest_desc) */
+typedef struct nconv_frame_ingest {
+    int B, h, w;
+    int reverse;                   /* != 0: rgb_out's planes in reverse channel order        */
+    const unsigned char* rgb;      /* NULL: no RGB                                           */
+    long long rgb_image_stride;    /* bytes (ignored when B == 1)                            */
+    long long rgb_row_stride;      /* bytes, >= 3 w                                          */
+    float* rgb_out;                /* (B, 3, h, w) contiguous fp32                           */
+    nconv_frame_plane plane[2];
+} nconv_frame_ingest_desc;
+
+int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream);
+
+/* A prediction as 16-bit fixed point (KITTI's submission format is a 16-bit PNG of depth x 256):
+ * out[b][i][j] = clamp(round_to_nearest_even(pred * scale), 0, 65535), NaN -> 0, the product one
+ * fp32 rounding. pred is fp32 with image / row strides in elements, as nconv_depth_metrics takes it
+ * (a cropped view such as DNET's output works); out is uint16 (B, 1, H, W) contiguous, 2-byte
+ * aligned. scale must be positive. One kernel, no workspace. */
+int nconv_depth_export_u16(const float* pred, long long image_stride, long long row_stride, int B, int H, int W,
+                           float scale, unsigned short* out, void* stream);
 
 #ifdef __cplusplus
 }

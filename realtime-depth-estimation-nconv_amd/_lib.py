@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NCONV_LIB: an alternative build of the same library (kernel-tuning experiments)
 LIB_PATH = os.environ.get("NCONV_LIB") or os.path.join(_HERE, "libnconv.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 BWD_ACCUMULATE = 1
 BWD_DEFER_REDUCE = 2
 BWD_SEPARATE = 4  # accepted and ignored since ABI 21 (include/nconv.h)
@@ -31,6 +31,8 @@ KERNEL_NAMES = ("generic", "tiled_fp32", "mfma_fp32", "mfma_bf16x3", "mfma_bf16x
 DENSE_3X3, DENSE_1X1, DENSE_TRANSPOSED_4X4, DENSE_CONV4X4_S2 = 0, 1, 2, 3
 # enum nconv_dense_math
 DENSE_MATHS = {"fp32": 0, "bf16x9": 2, "bf16x6": 3}
+# enum nconv_frame_dtype
+FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
 
 EXPORTED = (
     "nconv_abi_version",
@@ -71,6 +73,8 @@ EXPORTED = (
     "nconv_depth_loss_bwd",
     "nconv_depth_metrics_workspace_bytes",
     "nconv_depth_metrics",
+    "nconv_frame_ingest",
+    "nconv_depth_export_u16",
 )
 
 
@@ -125,6 +129,19 @@ class NconvBnTrain(ctypes.Structure):
                 ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
                 ("momentum", ctypes.c_float), ("eps", ctypes.c_float), ("relu", ctypes.c_int),
                 ("y", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p)]
+
+
+class NconvFramePlane(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("image_stride", ctypes.c_longlong), ("row_stride", ctypes.c_longlong),
+                ("dtype", ctypes.c_int), ("shift", ctypes.c_int), ("scale", ctypes.c_float),
+                ("out", ctypes.c_void_p)]
+
+
+class NconvFrameIngest(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("reverse", ctypes.c_int),
+                ("rgb", ctypes.c_void_p), ("rgb_image_stride", ctypes.c_longlong),
+                ("rgb_row_stride", ctypes.c_longlong), ("rgb_out", ctypes.c_void_p),
+                ("plane", NconvFramePlane * 2)]
 
 
 _lib = None
@@ -217,6 +234,10 @@ def _declare(lib):
     lib.nconv_depth_metrics_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_depth_metrics.restype = I
     lib.nconv_depth_metrics.argtypes = [P, L, L, P, L, L, I, I, I, F, F, F, F, P, P, P, ctypes.c_size_t, P]
+    lib.nconv_frame_ingest.restype = I
+    lib.nconv_frame_ingest.argtypes = [ctypes.POINTER(NconvFrameIngest), P]
+    lib.nconv_depth_export_u16.restype = I
+    lib.nconv_depth_export_u16.argtypes = [P, L, L, I, I, I, F, P, P]
 
 
 def lib():

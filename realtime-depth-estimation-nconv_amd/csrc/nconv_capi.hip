@@ -671,4 +671,70 @@ int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p
     return rc ? fail(rc, fn, why) : 0;
 }
 
+int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream) {
+    const char* fn = "nconv_frame_ingest";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->rgb && !d->plane[0].src && !d->plane[1].src) return fail(-22, fn, "nothing to do: no rgb and no planes");
+    if (d->B <= 0 || d->h <= 0 || d->w <= 0) return fail(-22, fn, "non-positive B/h/w");
+    if ((long long)d->B * d->h * d->w > (1LL << 30)) return fail(-22, fn, "batch too large");
+    const int B = d->B, h = d->h, w = d->w;
+    // a view's byte offsets inside one image are 32-bit (buffer loads); the image offsets are 64-bit
+    auto view = [&](long long bs, long long rs, long long row_bytes) -> const char* {
+        if (rs < row_bytes) return "row stride smaller than the row's bytes";
+        if (rs >= (1LL << 30) / h) return "plane too large";
+        if (B > 1 && bs < h * rs) return "image stride smaller than h * row stride";
+        return nullptr;
+    };
+    nconv::IngestArgs a{};
+    a.B = B, a.h = h, a.w = w, a.reverse = d->reverse != 0;
+    if (d->rgb) {
+        if (const char* why = view(d->rgb_image_stride, d->rgb_row_stride, 3LL * w)) return fail(-22, fn, why);
+        if (!d->rgb_out) return fail(-22, fn, "null rgb_out");
+        if ((size_t)d->rgb_out % 4) return fail(-22, fn, "rgb_out not 4-byte aligned");
+        a.rgb = d->rgb, a.rgb_bs = B > 1 ? d->rgb_image_stride : 0, a.rgb_rs = d->rgb_row_stride;
+        a.rgb_out = d->rgb_out;
+        a.rgb_fast = (size_t)a.rgb % 4 == 0 && a.rgb_rs % 4 == 0 && a.rgb_bs % 4 == 0;
+    }
+    for (int k = 0; k < 2; ++k) {
+        const nconv_frame_plane& p = d->plane[k];
+        if (!p.src) continue;
+        if (p.dtype != NCONV_FRAME_U8 && p.dtype != NCONV_FRAME_U16 && p.dtype != NCONV_FRAME_F32)
+            return fail(-22, fn, "unknown dtype (enum nconv_frame_dtype)");
+        const long long E = p.dtype == NCONV_FRAME_U8 ? 1 : p.dtype == NCONV_FRAME_U16 ? 2 : 4;
+        if (p.shift < 0 || p.shift > 15) return fail(-22, fn, "shift outside 0..15");
+        if (p.dtype == NCONV_FRAME_F32 && p.shift != 0) return fail(-22, fn, "non-zero shift with F32");
+        if (const char* why = view(p.image_stride, p.row_stride, E * w)) return fail(-22, fn, why);
+        const long long bs = B > 1 ? p.image_stride : 0;
+        if ((size_t)p.src % E || p.row_stride % E || bs % E)
+            return fail(-22, fn, "U16 / F32 plane not aligned to its element size");
+        if (!p.out) return fail(-22, fn, "null plane out");
+        if ((size_t)p.out % 4) return fail(-22, fn, "plane out not 4-byte aligned");
+        const long long A = p.dtype == NCONV_FRAME_F32 ? 16 : 4;
+        a.pl[k] = nconv::IngestPlane{(const unsigned char*)p.src, bs, p.row_stride, p.out, p.dtype, p.shift, p.scale,
+                                     (size_t)p.src % A == 0 && p.row_stride % A == 0 && bs % A == 0};
+    }
+    const char* why = nullptr;
+    int rc = nconv::launch_frame_ingest(a, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
+int nconv_depth_export_u16(const float* pred, long long image_stride, long long row_stride, int B, int H, int W,
+                           float scale, unsigned short* out, void* stream) {
+    const char* fn = "nconv_depth_export_u16";
+    if (!pred || !out) return fail(-22, fn, "null pred or out");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
+    if (row_stride < W) return fail(-22, fn, "row stride smaller than W");
+    if (row_stride >= (1LL << 29) / H) return fail(-22, fn, "plane too large");
+    if (B > 1 && image_stride < H * row_stride) return fail(-22, fn, "image stride smaller than H * row stride");
+    if (!(scale > 0.f) || scale == __builtin_inff()) return fail(-22, fn, "scale must be positive and finite");
+    if ((size_t)pred % 4 || (size_t)out % 2) return fail(-22, fn, "pred not 4-byte or out not 2-byte aligned");
+    const long long bs = B > 1 ? image_stride : 0;
+    const nconv::ExportArgs a{pred, bs, row_stride, B, H, W, (size_t)pred % 16 == 0 && row_stride % 4 == 0 && bs % 4 == 0,
+                              scale, out};
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_export(a, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

@@ -214,4 +214,34 @@ struct MetricsArgs {
 size_t metrics_workspace_bytes(int B, int H, int W);
 int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, hipStream_t st, const char** why);
 
+// Raw frame ingest (nconv_frame_ingest) and 16-bit depth export (nconv_depth_export_u16), frame_io.hip.
+struct IngestPlane {
+    const unsigned char* src;  // null: absent
+    long long bs, rs;          // image / row strides in bytes
+    float* out;                // (B, 1, h, w) contiguous
+    int dtype, shift;          // enum nconv_frame_dtype; right shift of the integer value
+    float scale;
+    int fast;  // base and strides allow the wide loads (4-byte aligned; F32: 16-byte aligned)
+};
+struct IngestArgs {
+    int B, h, w;
+    int reverse;               // RGB planes written in reverse channel order
+    const unsigned char* rgb;  // null: absent
+    long long rgb_bs, rgb_rs;  // bytes
+    float* rgb_out;            // (B, 3, h, w) contiguous
+    int rgb_fast;              // base and strides 4-byte aligned: 96-bit loads
+    IngestPlane pl[2];
+};
+int launch_frame_ingest(const IngestArgs& a, hipStream_t st, const char** why);
+
+struct ExportArgs {
+    const float* d;
+    long long bs, rs;  // image / row strides of d (elements)
+    int B, H, W;
+    int vec;           // d's image bases and rows are 16-byte aligned: 128-bit loads
+    float scale;
+    unsigned short* out;  // (B, 1, H, W) contiguous
+};
+int launch_depth_export(const ExportArgs& a, hipStream_t st, const char** why);
+
 }  // namespace nconv

@@ -53,6 +53,21 @@ def imread_gray(path, depth_decode="reference"):
     return ((rgb[..., 0] * 4899 + rgb[..., 1] * 9617 + rgb[..., 2] * 1868 + 8192) >> 14).astype(np.uint8)
 
 
+def imread_rgb_raw(path):
+    """The decoded uint8 (H, W, 3) image in RGB order (imread_bgr without the channel reversal)."""
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB")).copy()
+
+
+def imread_gray_raw(path):
+    """The values imread_gray decodes from, as stored: uint16 (H, W) of a 16-bit PNG, else uint8
+    (frames.ingest applies the depth_decode's shift and the / 256 on the device)."""
+    with Image.open(path) as im:
+        if im.mode in ("I;16", "I;16B", "I;16L", "I"):
+            return np.asarray(im).astype(np.uint16)
+    return imread_gray(path)
+
+
 def read_calib_file(filepath):
     """Read a KITTI calibration file into a dict of float arrays (kittiloader.py:9-23)."""
     data = {}
@@ -69,6 +84,9 @@ def read_calib_file(filepath):
 # ---- KITTI (dataset/kittiloader.py) ----------------------------------------------------------------
 class _KittiBase(Dataset):
     depth_decode = "reference"
+    # raw=True: samples carry the stored integers (rgb uint8 (h, w, 3) in RGB order, depth / gt uint16
+    # or uint8 (h, w)), cropped alike; frames.Ingest converts a batch of them on the device
+    raw = False
 
     def __len__(self):
         return len(self.depths)
@@ -77,9 +95,13 @@ class _KittiBase(Dataset):
         return self.get_item(idx)
 
     def get_rgb(self, rgb_path):
+        if self.raw:
+            return torch.from_numpy(imread_rgb_raw(rgb_path))
         return torch.FloatTensor(imread_bgr(rgb_path)).permute(2, 0, 1)
 
     def get_depth(self, depth_path):
+        if self.raw:
+            return torch.from_numpy(imread_gray_raw(depth_path))
         d = imread_gray(depth_path, self.depth_decode).astype(np.float32) / 256.0
         return torch.FloatTensor(np.expand_dims(d, axis=0))
 
@@ -87,9 +109,14 @@ class _KittiBase(Dataset):
 
     def _crop(self, rgb, k, *planes):
         """Bottom rows and centred columns (kittiloader.py:53-60), K shifted by the crop."""
-        tp = rgb.shape[1] - self.height
-        lp = (rgb.shape[2] - self.width) // 2
-        out = [t[:, tp:tp + self.height, lp:lp + self.width] for t in (rgb,) + planes]
+        if self.raw:  # (H, W, 3) / (H, W): sliced on the host and made contiguous
+            tp = rgb.shape[0] - self.height
+            lp = (rgb.shape[1] - self.width) // 2
+            out = [t[tp:tp + self.height, lp:lp + self.width].contiguous() for t in (rgb,) + planes]
+        else:
+            tp = rgb.shape[1] - self.height
+            lp = (rgb.shape[2] - self.width) // 2
+            out = [t[:, tp:tp + self.height, lp:lp + self.width] for t in (rgb,) + planes]
         if k is not None:
             k[0, 2] -= lp
             k[1, 2] -= tp
@@ -99,13 +126,13 @@ class _KittiBase(Dataset):
 class DataLoader_KITTI(_KittiBase):
     """KITTI depth completion train / val split (kittiloader.py:25-97)."""
 
-    def __init__(self, data_dir, mode, height=256, width=1216, tp_min=50, depth_decode="reference"):
+    def __init__(self, data_dir, mode, height=256, width=1216, tp_min=50, depth_decode="reference", raw=False):
         self.depth_path = os.path.join(data_dir, "data_depth_annotated", mode)
         self.lidar_path = os.path.join(data_dir, "data_depth_velodyne", mode)
         self.depths = list(sorted(glob.iglob(self.depth_path + "/**/*.png", recursive=True)))
         self.lidars = list(sorted(glob.iglob(self.lidar_path + "/**/*.png", recursive=True)))
         self.height, self.width, self.tp_min = height, width, tp_min
-        self.depth_decode = depth_decode
+        self.depth_decode, self.raw = depth_decode, raw
 
     def _rgb_path(self, index):
         f = self.depths[index].split("/")
@@ -134,13 +161,13 @@ class DataLoader_KITTI(_KittiBase):
 class DataLoader_KITTI_seltest(_KittiBase):
     """KITTI val_selection_cropped (kittiloader.py:100-154)."""
 
-    def __init__(self, data_dir, height=256, width=1216, tp_min=50, depth_decode="reference"):
+    def __init__(self, data_dir, height=256, width=1216, tp_min=50, depth_decode="reference", raw=False):
         base = os.path.join(data_dir, "val_selection_cropped")
         self.depths = list(sorted(glob.iglob(os.path.join(base, "groundtruth_depth") + "/*.png")))
         self.lidars = list(sorted(glob.iglob(os.path.join(base, "velodyne_raw") + "/*.png")))
         self.images = list(sorted(glob.iglob(os.path.join(base, "image") + "/*.png")))
         self.height, self.width, self.tp_min = height, width, tp_min
-        self.depth_decode = depth_decode
+        self.depth_decode, self.raw = depth_decode, raw
 
     def get_item(self, index):
         rgb = self.get_rgb(self.images[index])
@@ -160,13 +187,13 @@ class DataLoader_KITTI_seltest(_KittiBase):
 class DataLoader_KITTI_test(DataLoader_KITTI_seltest):
     """KITTI test_depth_completion_anonymous (kittiloader.py:157-210): no ground truth."""
 
-    def __init__(self, data_dir, height=352, width=1216, tp_min=50, depth_decode="reference"):
+    def __init__(self, data_dir, height=352, width=1216, tp_min=50, depth_decode="reference", raw=False):
         base = os.path.join(data_dir, "test_depth_completion_anonymous")
         self.lidars = list(sorted(glob.iglob(os.path.join(base, "velodyne_raw") + "/*.png")))
         self.images = list(sorted(glob.iglob(os.path.join(base, "image") + "/*.png")))
         self.depths = self.lidars
         self.height, self.width, self.tp_min = height, width, tp_min
-        self.depth_decode = depth_decode
+        self.depth_decode, self.raw = depth_decode, raw
 
     def get_item(self, index):
         rgb = self.get_rgb(self.images[index])
@@ -181,7 +208,7 @@ class DataLoader_NYU(Dataset):
     mask (use_mask) or with as many random points zeroed as the mask has zeros, optionally with
     +-10 % noise on 10 % of the points (add_noise), exactly as the reference."""
 
-    def __init__(self, data_dir, mode, use_mask, add_noise, height=480, width=640, tp_min=50):
+    def __init__(self, data_dir, mode, use_mask, add_noise, height=480, width=640, tp_min=50, raw=False):
         self.depth_path = os.path.join(data_dir, mode, "gt")
         self.lidar_path = os.path.join(data_dir, mode, "depth")
         self.rgb_path = os.path.join(data_dir, mode, "img")
@@ -192,6 +219,7 @@ class DataLoader_NYU(Dataset):
         self.masks = list(sorted(glob.iglob(self.mask_path + "/*.npy")))
         self.height, self.width, self.tp_min = height, width, tp_min
         self.use_mask, self.add_noise = use_mask, add_noise
+        self.raw = raw  # rgb as the decoded uint8 (h, w, 3) in RGB order (frames.Ingest); depth / gt unchanged
         self.k = np.array([[582.62448, 0.0, 313.04476], [0.0, 582.69103, 238.44390], [0.0, 0.0, 1.0]])
 
     def __len__(self):
@@ -205,9 +233,14 @@ class DataLoader_NYU(Dataset):
         depth = self.get_depth(self.lidars[index])
         gt = self.get_gt(self.depths[index])
         k = torch.FloatTensor(self.k)
-        tp = rgb.shape[1] - self.height
-        lp = (rgb.shape[2] - self.width) // 2
-        rgb = rgb[:, tp:tp + self.height, lp:lp + self.width]
+        if self.raw:
+            tp = rgb.shape[0] - self.height
+            lp = (rgb.shape[1] - self.width) // 2
+            rgb = rgb[tp:tp + self.height, lp:lp + self.width].contiguous()
+        else:
+            tp = rgb.shape[1] - self.height
+            lp = (rgb.shape[2] - self.width) // 2
+            rgb = rgb[:, tp:tp + self.height, lp:lp + self.width]
         depth = depth[:, tp:tp + self.height, lp:lp + self.width]
         gt = gt[:, tp:tp + self.height, lp:lp + self.width]
         k[0, 2] -= lp
@@ -216,6 +249,8 @@ class DataLoader_NYU(Dataset):
         return {"rgb": rgb, "depth": depth, "gt": gt, "k": k}
 
     def get_rgb(self, rgb_path):
+        if self.raw:
+            return torch.from_numpy(imread_rgb_raw(rgb_path))
         return torch.FloatTensor(imread_bgr(rgb_path)).permute(2, 0, 1)
 
     def get_depth(self, depth_path):
@@ -256,19 +291,22 @@ class DataLoader_NYU(Dataset):
 class DataLoader_NYU_test(Dataset):
     """NYU test split without ground truth (nyuloader.py:121-169); no crop."""
 
-    def __init__(self, data_dir, mode, height=640, width=480, tp_min=50):
+    def __init__(self, data_dir, mode, height=640, width=480, tp_min=50, raw=False):
         self.lidar_path = os.path.join(data_dir, mode, "depth")
         self.rgb_path = os.path.join(data_dir, mode, "img")
         self.lidars = list(sorted(glob.iglob(self.lidar_path + "/*.npy")))
         self.rgbs = list(sorted(glob.iglob(self.rgb_path + "/*.png")))
         self.height, self.width, self.tp_min = height, width, tp_min
         self.k = np.array([[329.64, 0.0, 318.0], [0.0, 328.62, 236.0], [0.0, 0.0, 1.0]])
+        self.raw = raw
 
     def __len__(self):
         return len(self.lidars)
 
     def __getitem__(self, idx):
-        return {"rgb": torch.FloatTensor(imread_bgr(self.rgbs[idx])).permute(2, 0, 1),
+        rgb = torch.from_numpy(imread_rgb_raw(self.rgbs[idx])) if self.raw else \
+            torch.FloatTensor(imread_bgr(self.rgbs[idx])).permute(2, 0, 1)
+        return {"rgb": rgb,
                 "depth": torch.FloatTensor(np.load(self.lidars[idx], allow_pickle=False).reshape(1, 480, 640)),
                 "k": torch.FloatTensor(self.k)}
 
@@ -280,8 +318,11 @@ class DevicePrefetcher:
     stream waits on that copy only when the batch is taken (train_step1.py:55-57 moves every batch
     with .to(device, non_blocking=True) from pageable memory, which serialises the copy)."""
 
-    def __init__(self, loader, device, keys=("rgb", "depth", "gt", "k")):
+    def __init__(self, loader, device, keys=("rgb", "depth", "gt", "k"), ingest=None):
         self.loader, self.device, self.keys = loader, torch.device(device), keys
+        # ingest: a callable on the device batch (frames.Ingest for raw=True loaders), run on the
+        # prefetch stream right after the copies, so the conversion overlaps the previous step too
+        self.ingest = ingest
         self.stream = torch.cuda.Stream(device=self.device)
 
     def _load(self, it):
@@ -296,6 +337,8 @@ class DevicePrefetcher:
                     out[k] = (v if v.is_pinned() else v.pin_memory()).to(self.device, non_blocking=True)
                 else:
                     out[k] = v
+            if self.ingest is not None:
+                out = self.ingest(out)
         return out
 
     def __iter__(self):
