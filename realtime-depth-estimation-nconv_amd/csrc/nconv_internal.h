@@ -114,7 +114,12 @@ struct RedJob {
 };
 constexpr int kMaxRedJobs = 16;
 constexpr int kSumChunks = 1024;
+constexpr int kReduceSplit = 16;  // slice-sum rows after a layer's partial rows (nconv_wgrad.hip)
 int launch_wgrad_reduce_multi(int n, const RedJob* jobs, hipStream_t st, const char** why);
+// one layer's nblk partial rows at part: reduced into a.gw / a.gb now, or (a.defer) left for a later
+// nconv_wgrad_reduce with *a.nparts = nblk
+int launch_wgrad_reduce(const BwdArgs& a, const float* part, int nblk, int nw, int cout, int fan,
+                        const float* wsum, hipStream_t st, const char** why);
 
 // Forward. Return 0, or a negative errno with *why set.
 int launch_fwd(const LayerDev& d, float* y, float* yc, float* py, float* pc, unsigned* parg, hipStream_t st,
@@ -154,6 +159,9 @@ int dev_cus();
 int dev_occupancy(const void* kernel, int threads, size_t dyn_lds);
 
 // Backward.
+inline bool is_upcat(const nconv_layer& L) {
+    return L.load_mode == NCONV_LOAD_UPCAT_SKIP_FIRST || L.load_mode == NCONV_LOAD_UPCAT_UP_FIRST;
+}
 size_t bwd_workspace_bytes(const LayerDev& d);
 // weight gradient on the bf16 matrix cores (nconv_wgrad_bf.hip): np = 2 (bf16x3) or 3 (bf16x9) split
 // parts; at most max_blocks partial rows into part; returns the number written
@@ -162,6 +170,26 @@ int go_wgrad_bf(const LayerDev& d, const BwdArgs& a, float* part, int max_blocks
 // input gradient on the bf16 matrix cores (nconv_dgrad_bf.hip), np as go_wgrad_bf
 template <int CIN, int COUT, int K, int MODE>
 void go_dgrad_bf(const LayerDev& d, const BwdArgs& a, float* tmp_x, float* tmp_c, int np, hipStream_t st);
+// exact-fp32 input gradient (nconv_dgrad.hip): dgrad_tiled, or dgrad_phase where dgrad_phase_ok(L);
+// GP: pooled-gradient routing, HW: fused nconv1 weight gradient (its partial rows reduced or, with
+// a.defer, counted in *a.hnparts), T7: fused nconv7 backward. tx / tc: the staged upsampled planes.
+bool dgrad_phase_ok(const nconv_layer& L);
+size_t dgrad_blocks(const nconv_layer& L);  // workgroups of the tiled / phase input gradient
+template <int CIN, int COUT, int K, int MODE, bool GP, bool HW, bool T7>
+int go_dgrad(const LayerDev& d, const BwdArgs& a, float* tx, float* tc, hipStream_t st, const char** why);
+int launch_dgrad_generic(const LayerDev& d, const BwdArgs& a, float* tx, float* tc, hipStream_t st,
+                         const char** why);
+void launch_upsample_bwd_gather(const LayerDev& d, const BwdArgs& a, const float* tx, const float* tc,
+                                hipStream_t st);
+// exact-fp32 weight-gradient partial rows into part, returning their number: wgrad_tiled (<=
+// max_blocks); wgrad_mfma / wgrad_mfma2 (<= wgrad_mfma_max_blocks; T7: nconv7's rows to a.t7part too)
+template <int CIN, int COUT, int K, int MODE>
+int go_wgrad_tiled(const LayerDev& d, const BwdArgs& a, float* part, int max_blocks, hipStream_t st);
+template <int CIN, int COUT, int K, int MODE, bool GP, bool T7>
+int go_wgrad_mfma(const LayerDev& d, const BwdArgs& a, float* part, hipStream_t st);
+size_t wgrad_mfma_max_blocks(const nconv_layer& L);
+int launch_wgrad_generic(const LayerDev& d, const BwdArgs& a, float* part, int nchunk, hipStream_t st,
+                         const char** why);
 int launch_bwd(const LayerDev& d, const BwdArgs& a, hipStream_t st, const char** why);
 // nconv1's weight-gradient partial rows of the fused head (200 weights, 8 sum gy, 8 sum gcout*cout)
 constexpr int kHeadNw = 8 * 25, kHeadStride = kHeadNw + 16;

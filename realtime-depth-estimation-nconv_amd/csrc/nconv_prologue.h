@@ -74,7 +74,7 @@ struct PhaseArgs {
 };
 
 // Box weights of an exactly-2x UPCAT layer's upsampled half for the phase-form input gradient
-// (dgrad_phase, nconv_bwd.hip): entry e = [o][i][t][u] (8 x 8 x 4 x 4) = the sum of W[o][first_up +
+// (dgrad_phase, nconv_dgrad.hip): entry e = [o][i][t][u] (8 x 8 x 4 x 4) = the sum of W[o][first_up +
 // i][kh][kw] over kh in S(t), kw in S(u), S(0) = {2}, S(1) = {1, 2}, S(2) = {0, 1}, S(3) = {0}
 // (row-major order). Shared by the box_weights launch and the training prologue (bitwise equal).
 __device__ __forceinline__ float box_weight(const float* w, int first_up, int e) {

@@ -1,6 +1,6 @@
 // nconv_wgrad_bf.hip — NConv weight gradient on the bf16 matrix cores with split operands (gfx950).
 //
-// The same GEMM as wgrad_mfma (nconv_bwd.hip), per output row oh, over the column index
+// The same GEMM as wgrad_mfma (nconv_wgrad_mfma.hip), per output row oh, over the column index
 // q = ow - o0 + kw of a strip of output columns [o0, o0 + OW):
 //     gW[(kh, i)][(kw, o)] += sum_q  XC[i][oh+kh-PH][o0+q-PW] * gN[o][oh][o0+q-kw]  +  C[...] * gD[...]
 // (gN, gD zero outside the strip's own columns, so every output column is counted once) on

@@ -92,7 +92,7 @@ def test_training_input_gradients_occupancy(tmp_path):
     waves per SIMD and the tail's (dgrad_phase) at six: the one-plane-ahead stagers' register budgets
     and the head epilogue's halved LDS (profiles/r5_ab_dgrad_occupancy.log,
     r5_ab_dgrad_phase_one_ahead.log). A change that pushes them back to four waves shows here."""
-    md = _kernel_blocks(os.path.join(BUILD, "nconv_bwd.hip.o"), str(tmp_path))
+    md = _kernel_blocks(os.path.join(BUILD, "nconv_dgrad.hip.o"), str(tmp_path))
     head = [v for k, v in md.items() if "dgrad_tiledILi8ELi8ELi5ELi0ELb1ELb1E" in k]
     phase = [v for k, v in md.items() if "dgrad_phaseILi4ELb1E" in k]
     assert len(head) == 1 and len(phase) == 1, sorted(md)
