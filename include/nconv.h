@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NCONV_ABI_VERSION 25
+#define NCONV_ABI_VERSION 26
 
 /* How a layer's input (data x, confidence c) is produced from its source tensors. These are the
  * DNET glue ops fused into the layer's load stage (models/step1.py:53,61-90). */
@@ -590,6 +590,78 @@ int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream);
  * aligned. scale must be positive. One kernel, no workspace. */
 int nconv_depth_export_u16(const float* pred, long long image_stride, long long row_stride, int B, int H, int W,
                            float scale, unsigned short* out, void* stream);
+
+/* ABI 26. A completed depth map and the camera intrinsics -> a metric 3-D point cloud. The reference
+ * has no counterpart: its loaders return the 3x3 intrinsics `k` of every frame, principal point
+ * shifted by the crop (this package's data.py:121-122, 246-247; dataset/kittiloader.py), and nothing
+ * reads them. With PyTorch ops the same result is a meshgrid, three elementwise passes, a boolean-mask
+ * index and a host synchronisation for the point count.
+ * Pixel (b, i, j) with z = depth[b][i][j] is valid iff
+ *     z > z_min && z <= z_max && (conf == NULL || conf[b][i][j] >= conf_min)
+ * (comparisons: a NaN depth or confidence is not valid) and its point is
+ *     x = ((float)j - cx) * z / fx,   y = ((float)i - cy) * z / fy,   z
+ * each operation one fp32 rounding in that order, the division IEEE. fx, fy, cx, cy = K[0][0],
+ * K[1][1], K[0][2], K[1][2] of image b's row-major 3x3 matrix at k + b * k_image_stride, read on the
+ * device; the other five entries of K are NOT read (no skew, no distortion). k_image_stride = 0: one
+ * camera for the whole batch.
+ * depth, conf: fp32 (B, H, W) views, image / row strides in elements (a cropped view such as DNET's
+ * output works), 4-byte aligned. color (optional), by color_kind:
+ *   NCONV_COLOR_F32_PLANAR      fp32 (B, 3, H, W) view, image / channel / row strides in floats (the
+ *                               tensors the models take); a value v becomes clamp(rintf(v), 0, 255),
+ *                               NaN -> 0
+ *   NCONV_COLOR_U8_INTERLEAVED  uint8 (B, H, W, 3), image / row strides in bytes (the raw=True
+ *                               loaders' frames); color_channel_stride is ignored
+ * and the point's colour is 3 x uint8 in the source's channel order, reversed when reverse != 0.
+ * The zero value of every optional field is "absent / default": conf NULL = no gate, color NULL /
+ * NCONV_COLOR_NONE = no colour, conf_min 0, z_min 0, z_max 0 (beside a z_min >= 0, where it would
+ * select nothing) = FLT_MAX, so +inf is not valid.
+ * No byte outside a view's extent is read; wide loads where base and strides are 16-byte aligned
+ * (U8: 4-byte), element-wide range-checked loads otherwise. */
+enum nconv_color_kind { NCONV_COLOR_NONE = 0, NCONV_COLOR_F32_PLANAR = 1, NCONV_COLOR_U8_INTERLEAVED = 2 };
+
+typedef struct nconv_backproject {
+    int B, H, W;
+    int color_kind;                  /* enum nconv_color_kind; NONE with color == NULL            */
+    const float* depth;
+    long long depth_image_stride;    /* elements (ignored when B == 1)                            */
+    long long depth_row_stride;      /* elements, >= W                                            */
+    const float* conf;               /* NULL: no confidence gate                                  */
+    long long conf_image_stride;
+    long long conf_row_stride;
+    const void* color;               /* NULL: no colour                                           */
+    long long color_image_stride;    /* elements of the colour's type (ignored when B == 1)       */
+    long long color_channel_stride;  /* F32_PLANAR only, >= H * row stride                        */
+    long long color_row_stride;      /* >= W (F32_PLANAR) / >= 3 W (U8_INTERLEAVED)               */
+    int reverse;                     /* != 0: the point's three colour bytes in reverse order     */
+    float z_min;                     /* valid: z > z_min                                          */
+    float z_max;                     /* ... && z <= z_max; 0 (with z_min >= 0): FLT_MAX           */
+    float conf_min;                  /* ... && conf >= conf_min                                   */
+    const float* k;                  /* (3, 3) or (B, 3, 3) fp32 row-major, on the device         */
+    long long k_image_stride;        /* floats; 0: one camera for the batch                       */
+} nconv_backproject;
+
+/* The organised form for consumers that keep the image grid (normals, meshing, reprojection): xyz
+ * (B, 3, H, W) contiguous fp32, planes x, y, z; a pixel that is not valid is NaN in all three.
+ * color is ignored. One kernel, no workspace. */
+int nconv_backproject_map(const nconv_backproject* d, float* xyz, void* stream);
+
+/* The packed form robotics / mapping consumers take: the valid pixels' points in raster order inside
+ * an image, images in batch order, identical on every run (no atomics: the order comes from a scan).
+ *   xyz      (capacity, 3) fp32, interleaved
+ *   rgb      (capacity, 3) uint8; NULL: skip (d->color is then not read); with rgb != NULL
+ *            d->color must be given
+ *   index    (capacity) int32 = (b * H + i) * W + j of each point; NULL: skip
+ *   offsets  (B + 1) int32: image b's points are [offsets[b], offsets[b + 1]); offsets[B] is the TRUE
+ *            number of valid pixels, also when it exceeds capacity: points of rank >= capacity are
+ *            not written, so the caller detects truncation without a second run.
+ * B * H * W must be < 2^31, and the B * H * ceil(W / 256) segments at most 2^24 (-EINVAL above).
+ * workspace: nconv_backproject_workspace_bytes(B, H, W) bytes (0 for invalid sizes), 4-byte
+ * aligned, overwritten. Three kernels on `stream` (count, scan, write), no host synchronisation, no
+ * waiting between workgroups. xyz may be NULL when capacity is 0. */
+size_t nconv_backproject_workspace_bytes(int B, int H, int W);
+int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned char* rgb, int* index,
+                             long long capacity, int* offsets, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }

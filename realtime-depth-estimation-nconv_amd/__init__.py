@@ -7,13 +7,14 @@ kernels behind the C ABI of include/nconv.h (libnconv.so, built in-tree).
 The directory name is not a Python identifier; import it through the repo-root helper
 `nconv_pkg.load()`, which registers it as the module `nconv_amd`.
 """
-from . import _lib, data, dense, dp, export, frames, guided, metrics, train
+from . import _lib, data, dense, dp, export, frames, guided, metrics, pointcloud, train
 from .nconv import EnforcePos, LayerSpec, NConv2d, NConvLayerFn, nconv_layer, weight_prep
 from .dnet import DNET, SETP1_NCONV, crop_hw
 from .guided import SETP2_BP_EXPORT, SETP2_BP_TRAIN, RGBEncoder
 from .metrics import DepthMetrics, depth_metric_sums
 from .frames import Ingest, export_depth16, ingest, write_depth_png16
+from .pointcloud import PointCloud, backproject, backproject_map, write_ply
 
-__all__ = ["EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
+__all__ = ["PointCloud", "backproject", "backproject_map", "write_ply","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
            "SETP1_NCONV", "crop_hw", "SETP2_BP_EXPORT", "SETP2_BP_TRAIN", "RGBEncoder", "DepthMetrics",
            "depth_metric_sums", "Ingest", "export_depth16", "ingest", "write_depth_png16"]

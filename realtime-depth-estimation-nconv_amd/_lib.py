@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NCONV_LIB: an alternative build of the same library (kernel-tuning experiments)
 LIB_PATH = os.environ.get("NCONV_LIB") or os.path.join(_HERE, "libnconv.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 BWD_ACCUMULATE = 1
 BWD_DEFER_REDUCE = 2
 BWD_SEPARATE = 4  # accepted and ignored since ABI 21 (include/nconv.h)
@@ -33,6 +33,8 @@ DENSE_3X3, DENSE_1X1, DENSE_TRANSPOSED_4X4, DENSE_CONV4X4_S2 = 0, 1, 2, 3
 DENSE_MATHS = {"fp32": 0, "bf16x9": 2, "bf16x6": 3}
 # enum nconv_frame_dtype
 FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
+# enum nconv_color_kind
+COLOR_NONE, COLOR_F32_PLANAR, COLOR_U8_INTERLEAVED = 0, 1, 2
 
 EXPORTED = (
     "nconv_abi_version",
@@ -75,6 +77,9 @@ EXPORTED = (
     "nconv_depth_metrics",
     "nconv_frame_ingest",
     "nconv_depth_export_u16",
+    "nconv_backproject_map",
+    "nconv_backproject_workspace_bytes",
+    "nconv_backproject_points",
 )
 
 
@@ -142,6 +147,17 @@ class NconvFrameIngest(ctypes.Structure):
                 ("rgb", ctypes.c_void_p), ("rgb_image_stride", ctypes.c_longlong),
                 ("rgb_row_stride", ctypes.c_longlong), ("rgb_out", ctypes.c_void_p),
                 ("plane", NconvFramePlane * 2)]
+
+
+class NconvBackproject(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("color_kind", ctypes.c_int),
+                ("depth", ctypes.c_void_p), ("depth_image_stride", ctypes.c_longlong),
+                ("depth_row_stride", ctypes.c_longlong), ("conf", ctypes.c_void_p),
+                ("conf_image_stride", ctypes.c_longlong), ("conf_row_stride", ctypes.c_longlong),
+                ("color", ctypes.c_void_p), ("color_image_stride", ctypes.c_longlong),
+                ("color_channel_stride", ctypes.c_longlong), ("color_row_stride", ctypes.c_longlong),
+                ("reverse", ctypes.c_int), ("z_min", ctypes.c_float), ("z_max", ctypes.c_float),
+                ("conf_min", ctypes.c_float), ("k", ctypes.c_void_p), ("k_image_stride", ctypes.c_longlong)]
 
 
 _lib = None
@@ -238,6 +254,12 @@ def _declare(lib):
     lib.nconv_frame_ingest.argtypes = [ctypes.POINTER(NconvFrameIngest), P]
     lib.nconv_depth_export_u16.restype = I
     lib.nconv_depth_export_u16.argtypes = [P, L, L, I, I, I, F, P, P]
+    lib.nconv_backproject_map.restype = I
+    lib.nconv_backproject_map.argtypes = [ctypes.POINTER(NconvBackproject), P, P]
+    lib.nconv_backproject_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_backproject_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_backproject_points.restype = I
+    lib.nconv_backproject_points.argtypes = [ctypes.POINTER(NconvBackproject), P, P, P, L, P, P, ctypes.c_size_t, P]
 
 
 def lib():

@@ -737,4 +737,105 @@ int nconv_depth_export_u16(const float* pred, long long image_stride, long long 
     return rc ? fail(rc, fn, why) : 0;
 }
 
+// The descriptor of nconv_backproject_map / _points checked and turned into the kernels' arguments
+// (with_color: the colour view is needed); NULL, or the reason it is invalid.
+static const char* backproject_args(const nconv_backproject* d, bool with_color, nconv::BackprojectArgs& a) {
+    if (!d) return "null descriptor";
+    if (!d->depth || !d->k) return "null depth or k";
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return "non-positive B/H/W";
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return "batch too large: B * H * W must be below 2^31";
+    if (nconv::backproject_segments(B, H, W) > (1LL << 24)) return "batch too large: more than 2^24 segments";
+    if (d->k_image_stride < 0) return "negative k image stride";
+    // z_max = 0 beside a z_min >= 0 would select nothing: that pair is the absent upper bound
+    const float z_max = d->z_max == 0.f && d->z_min >= 0.f ? __FLT_MAX__ : d->z_max;
+    if (!(z_max >= d->z_min)) return "z_max < z_min (or NaN)";
+    if (d->conf_min != d->conf_min) return "conf_min is NaN";
+    // a view's byte offsets inside one image are 32-bit (buffer loads); the image offsets are 64-bit
+    auto view = [&](long long bs, long long rs, long long row, long long elem) -> const char* {
+        if (rs < row) return "row stride smaller than W";
+        if (rs >= (1LL << 31) / elem / H) return "plane too large: extent of 2^31 bytes or more";
+        if (B > 1 && bs < H * rs) return "image stride smaller than H * row stride";
+        return nullptr;
+    };
+    auto vec = [&](const void* q, long long bs, long long rs) {
+        return (size_t)q % 16 == 0 && rs % 4 == 0 && (B == 1 || bs % 4 == 0);
+    };
+    a = nconv::BackprojectArgs{};
+    a.B = B, a.H = H, a.W = W, a.nseg = (int)nconv::backproject_segments(B, H, W);
+    if (const char* why = view(d->depth_image_stride, d->depth_row_stride, W, 4)) return why;
+    if ((size_t)d->depth % 4 || (size_t)d->k % 4) return "depth or k not 4-byte aligned";
+    a.depth = d->depth, a.dbs = B > 1 ? d->depth_image_stride : 0, a.drs = d->depth_row_stride;
+    a.d_vec = vec(d->depth, a.dbs, a.drs);
+    if (d->conf) {
+        if (const char* why = view(d->conf_image_stride, d->conf_row_stride, W, 4)) return why;
+        if ((size_t)d->conf % 4) return "conf not 4-byte aligned";
+        a.conf = d->conf, a.cbs = B > 1 ? d->conf_image_stride : 0, a.crs = d->conf_row_stride;
+        a.c_vec = vec(d->conf, a.cbs, a.crs);
+    }
+    if (d->color_kind != NCONV_COLOR_NONE && d->color_kind != NCONV_COLOR_F32_PLANAR &&
+        d->color_kind != NCONV_COLOR_U8_INTERLEAVED)
+        return "unknown color kind (enum nconv_color_kind)";
+    if ((d->color != nullptr) != (d->color_kind != NCONV_COLOR_NONE)) return "color and color_kind: both or neither";
+    if (with_color) {
+        if (!d->color) return "rgb output without a color source";
+        a.color = d->color, a.color_kind = d->color_kind, a.reverse = d->reverse != 0;
+        a.obs = B > 1 ? d->color_image_stride : 0, a.ors = d->color_row_stride;
+        if (d->color_kind == NCONV_COLOR_F32_PLANAR) {
+            if (const char* why = view(d->color_image_stride, d->color_row_stride, W, 4)) return why;
+            if (d->color_channel_stride < H * d->color_row_stride) return "channel stride smaller than H * row stride";
+            if (B > 1 && d->color_image_stride < 2 * d->color_channel_stride + H * d->color_row_stride)
+                return "image stride smaller than H * row stride";
+            if ((size_t)d->color % 4) return "color not 4-byte aligned";
+            a.ocs = d->color_channel_stride;
+            a.o_fast = vec(d->color, a.obs, a.ors) && a.ocs % 4 == 0;
+        } else {
+            if (const char* why = view(d->color_image_stride, d->color_row_stride, 3LL * W, 1)) return why;
+            a.o_fast = (size_t)d->color % 4 == 0 && a.ors % 4 == 0 && a.obs % 4 == 0;
+        }
+    }
+    a.k = d->k, a.kbs = d->k_image_stride;
+    a.z_min = d->z_min, a.z_max = z_max, a.conf_min = d->conf_min;
+    return nullptr;
+}
+
+int nconv_backproject_map(const nconv_backproject* d, float* xyz, void* stream) {
+    const char* fn = "nconv_backproject_map";
+    nconv::BackprojectArgs a;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (!xyz) return fail(-22, fn, "null xyz");
+    if ((size_t)xyz % 4) return fail(-22, fn, "xyz not 4-byte aligned");
+    const char* why = nullptr;
+    int rc = nconv::launch_backproject_map(a, xyz, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
+size_t nconv_backproject_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    if (nconv::backproject_segments(B, H, W) > (1LL << 24)) return 0;
+    return nconv::backproject_workspace_bytes(B, H, W);
+}
+
+int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned char* rgb, int* index,
+                             long long capacity, int* offsets, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    const char* fn = "nconv_backproject_points";
+    nconv::BackprojectArgs a;
+    if (const char* why = backproject_args(d, rgb != nullptr, a)) return fail(-22, fn, why);
+    if (capacity < 0) return fail(-22, fn, "negative capacity");
+    if (!xyz && capacity > 0) return fail(-22, fn, "null xyz");
+    if (!offsets) return fail(-22, fn, "null offsets");
+    if ((size_t)xyz % 4 || (size_t)index % 4 || (size_t)offsets % 4)
+        return fail(-22, fn, "xyz / index / offsets not 4-byte aligned");
+    if (!workspace || workspace_bytes < nconv::backproject_workspace_bytes(a.B, a.H, a.W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 4) return fail(-22, fn, "workspace not 4-byte aligned");
+    // every rank is below B * H * W < 2^31
+    const int cap = (int)(capacity < 0x7fffffffLL ? capacity : 0x7fffffffLL);
+    const char* why = nullptr;
+    int rc = nconv::launch_backproject_points(a, xyz, rgb, index, cap, offsets, (int*)workspace, (hipStream_t)stream,
+                                              &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

@@ -272,4 +272,27 @@ struct ExportArgs {
 };
 int launch_depth_export(const ExportArgs& a, hipStream_t st, const char** why);
 
+// Back-projection of a depth map to 3-D points (nconv_backproject_map / _points), backproject.hip.
+struct BackprojectArgs {
+    int B, H, W;
+    int nseg;                // B * H * ceil(W / 256) segments of 256 row pixels, one wave each
+    const float* depth;
+    long long dbs, drs;      // image / row strides of depth (elements)
+    const float* conf;       // null: no confidence gate
+    long long cbs, crs;
+    const void* color;       // null: none; else per color_kind
+    int color_kind, reverse;
+    long long obs, ocs, ors; // image / channel / row strides of the colour (elements of its type)
+    const float* k;
+    long long kbs;           // image stride of K in floats (0: one camera)
+    int d_vec, c_vec;        // image bases and rows 16-byte aligned: 128-bit loads
+    int o_fast;              // colour base and strides allow the wide loads (F32: 16-byte, U8: 4-byte)
+    float z_min, z_max, conf_min;
+};
+long long backproject_segments(int B, int H, int W);
+size_t backproject_workspace_bytes(int B, int H, int W);
+int launch_backproject_map(const BackprojectArgs& a, float* xyz, hipStream_t st, const char** why);
+int launch_backproject_points(const BackprojectArgs& a, float* xyz, unsigned char* rgb, int* index, int capacity,
+                              int* offsets, int* ws, hipStream_t st, const char** why);
+
 }  // namespace nconv

@@ -590,6 +590,35 @@ class DNET(nn.Module):
         xo, co = f(l7.spec(), xo, co, None, None, l7.weight, l7.bias, s7)
         return xo[:, :, 1:1 + out_h, 1:1 + out_w]
 
+    def forward_with_confidence(self, S):
+        """(depth, confidence), both (B, 1, out_h, out_w): forward(S)'s prediction, bit for bit,
+        and the confidence nconv7 propagates beside it (step1.py:92 computes it, :94 drops it),
+        cropped like the depth; 0 where the crop reaches nconv7's zero border. Inference only: it
+        raises where gradients would be recorded, and takes the fused inference path (nconv_fwd_tail
+        writes both), which needs min(H, W) >= 16."""
+        if torch.is_grad_enabled() and (S.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("DNET.forward_with_confidence is inference only: call it under torch.no_grad() "
+                               "(the output confidence has no backward)")
+        _require_device(S, "DNET.forward_with_confidence")
+        if S.dim() != 4 or S.shape[1] != 1:
+            raise ValueError(f"DNET expects (B, 1, H, W) sparse depth, got {tuple(S.shape)}")
+        H, W = S.shape[2], S.shape[3]
+        if min(H, W) < 16:
+            raise ValueError(f"DNET.forward_with_confidence needs min(H, W) >= 16 (the fused inference path), got "
+                             f"{H} x {W}")
+        S = S.contiguous()
+        layers = [getattr(self, n) for n in LAYERS]
+        out_h, out_w = crop_hw(H, W, self.crop)
+        out = torch.empty((S.shape[0], 1, out_h, out_w), device=S.device, dtype=torch.float32)
+        out_c = torch.empty_like(out)
+        pro = self._eval_prologue(layers, S)
+        if pro is None:
+            wsum, wph, w21 = self._prologue(layers, S), self._phase_weights(S.device), None
+        else:
+            wsum, wph, w21 = pro
+        self._infer_split(S, layers, wsum, out, wph, w21, out_c=out_c)
+        return out, out_c
+
     # -- inference ------------------------------------------------------------------------------
     # Exact-fp32 inference convolves the nearest-2x-upsampled half of nconv4/5/6's inputs at its
     # own resolution with phase weights (include/nconv.h nconv_layer.wphase; the kernel uses them
@@ -660,15 +689,16 @@ class DNET(nn.Module):
             cache[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
         return cache[key]
 
-    def _infer_split(self, S, layers, wsum, out, wph=None, w21=None):
+    def _infer_split(self, S, layers, wsum, out, wph=None, w21=None, out_c=None):
         """The inference chain on batch slices, one stream each (the weight prologue once, on the
         current stream, before the fork: a prologue per stream measured slower, 16.3-16.5 k against
-        16.9-17.2 k frames/s, profiles/r5_ab_stream_prologue.log)."""
+        16.9-17.2 k frames/s, profiles/r5_ab_stream_prologue.log). out_c: the output confidence,
+        written per slice like out (forward_with_confidence), or None."""
         B = S.shape[0]
         n = self._n_streams(B)
         bounds = self.split_bounds(B, n, self.inference_shares, self._configured_streams())
         if n == 1:
-            self._infer(S, layers, wsum, out, wph, w21=w21)
+            self._infer(S, layers, wsum, out, wph, w21=w21, out_c=out_c)
             return
         cur = torch.cuda.current_stream(S.device)
         side = self._side_streams(S.device, n - 1)
@@ -679,15 +709,17 @@ class DNET(nn.Module):
                 continue
             with torch.cuda.stream(st):
                 Sk = S[bounds[k]:bounds[k + 1]]
-                self._infer(Sk, layers, wsum, out[bounds[k]:bounds[k + 1]], wph, w21=w21)
+                ck = None if out_c is None else out_c[bounds[k]:bounds[k + 1]]
+                self._infer(Sk, layers, wsum, out[bounds[k]:bounds[k + 1]], wph, w21=w21, out_c=ck)
         for st in side:
             cur.wait_stream(st)
 
-    def _infer(self, S, layers, wsum, out, wph=None, w21=None):
+    def _infer(self, S, layers, wsum, out, wph=None, w21=None, out_c=None):
         """The inference chain on the current stream: each producer also writes the pooled input
-        of the next down layer, and nconv6+nconv7+crop run as one launch writing `out`. wph: the
-        phase weights of nconv4/5/6 (_phase_weights) or None. w21: the exact head's weights when
-        the prologue already built them (_eval_prologue), else built here."""
+        of the next down layer, and nconv6+nconv7+crop run as one launch writing `out` (and, with
+        out_c, nconv7's confidence beside it). wph: the phase weights of nconv4/5/6
+        (_phase_weights) or None. w21: the exact head's weights when the prologue already built
+        them (_eval_prologue), else built here."""
         (l1, l2, d1, d2, d3, l4, l5, l6, l7) = layers
         (s1, s2, sd1, sd2, sd3, s4, s5, s6, s7) = wsum
         w4, w5, w6 = (None, None, None) if wph is None else tuple(wph)
@@ -708,7 +740,7 @@ class DNET(nn.Module):
         if self.capture is not None:
             self.capture.update(down1=(x1, c1), down2=(x2, c2), down3=(x3, c3))
         x23, c23 = f(l5.spec(_lib.UPCAT_SKIP_FIRST), x2, c2, x34, c34, l5.weight, l5.bias, s5, wphase=w5)
-        self._fused_tail(l6, l7, s6, s7, x1, c1, x23, c23, out, w6)
+        self._fused_tail(l6, l7, s6, s7, x1, c1, x23, c23, out, w6, out_c=out_c)
 
     # Inference evaluates nconv1 inside nconv2's kernel (nconv_fwd_head) when the layers have
     # DNET's geometry -- in exact fp32 with nconv1 on the nonzero taps only and nconv2's confidence
@@ -727,17 +759,22 @@ class DNET(nn.Module):
             (8, 8, (5, 5), (2, 2), (1, 1)) and tuple(l1.dilation) == (1, 1) and tuple(l2.dilation) == (1, 1) \
             and l1.groups == 1 and l2.groups == 1
 
-    def _fused_tail(self, l6, l7, s6, s7, x1, c1, x23, c23, out, w6=None):
-        """nconv6 + nconv7 + crop into `out` (nconv_fwd_tail)."""
+    def _fused_tail(self, l6, l7, s6, s7, x1, c1, x23, c23, out, w6=None, out_c=None):
+        """nconv6 + nconv7 + crop into `out` (nconv_fwd_tail); out_c (of out's shape, contiguous)
+        receives nconv7's confidence at the same pixels, 0 in nconv7's zero border."""
         out_h, out_w = out.shape[2], out.shape[3]
         if out_h == 0 or out_w == 0 or out.shape[0] == 0:
             return out
+        if out_c is not None and not (out_c.shape == out.shape and out_c.is_contiguous() and
+                                      out_c.dtype == torch.float32 and out_c.device == out.device):
+            raise RuntimeError("fused tail: out_c must be a contiguous fp32 tensor of out's shape and device")
         L = l6.spec(_lib.UPCAT_UP_FIRST).descriptor(x1, c1, x23, c23, l6.weight, l6.bias, s6, w6)
         if tuple(l7.kernel_size) != (1, 1) or l7.padding[0] != l7.padding[1] or tuple(l7.stride) != (1, 1):
             raise RuntimeError("fused tail needs nconv7 = 1x1, stride 1, square padding")
         rc = _lib.lib().nconv_fwd_tail(
             _lib.ctypes.byref(L), _lib.ptr(l7.weight), _lib.ptr(l7.bias), _lib.ptr(s7), l7.in_channels,
-            l7.padding[0], l7.eps, _lib.ptr(out), None, out_h, out_w, 1, None, None, _lib.stream_handle(x1.device))
+            l7.padding[0], l7.eps, _lib.ptr(out), _lib.ptr(out_c), out_h, out_w, 1, None, None,
+            _lib.stream_handle(x1.device))
         _lib.check(rc, "nconv_fwd_tail")
         return out
 
@@ -758,3 +795,7 @@ class SETP1_NCONV(nn.Module):
         if more:
             x0_d = torch.cat((x0_d,) + tuple(more), dim=0)
         return self.d_net(x0_d)
+
+    def forward_with_confidence(self, x0_d):
+        """(depth, confidence) of d_net on one batch of sparse depth (DNET.forward_with_confidence)."""
+        return self.d_net.forward_with_confidence(x0_d)
