@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NCONV_ABI_VERSION 26
+#define NCONV_ABI_VERSION 27
 
 /* How a layer's input (data x, confidence c) is produced from its source tensors. These are the
  * DNET glue ops fused into the layer's load stage (models/step1.py:53,61-90). */
@@ -662,6 +662,69 @@ size_t nconv_backproject_workspace_bytes(int B, int H, int W);
 int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned char* rgb, int* index,
                              long long capacity, int* offsets, void* workspace, size_t workspace_bytes,
                              void* stream);
+
+/* ABI 27. An unordered LiDAR scan and a 3x4 projection -> the sparse depth plane S the models take,
+ * the inverse of nconv_backproject_points and under the same convention (pixel centres at integer
+ * coordinates, one fp32 rounding per operation). The reference has no counterpart: it reads S from
+ * KITTI's velodyne_raw PNGs, rasterised offline. With PyTorch ops the same result is a matmul, three
+ * elementwise passes and a boolean mask, a scatter_reduce_(amin) and a fix-up of the empty pixels,
+ * with no defined winner between points that tie.
+ * Inputs:
+ *   points   fp32 rows of point_stride floats, point_stride >= 3 (and <= 2^20); only the first three
+ *            floats (x, y, z) of a row are read: KITTI's .bin scans have point_stride 4, the xyz of
+ *            nconv_backproject_points 3. 4-byte aligned; no byte outside
+ *            [points, points + ((n_rows - 1) * point_stride + 3) * 4) is read.
+ *   offsets  (B + 1) int32 on the device, non-decreasing, offsets[B] <= n_rows: image b owns the rows
+ *            [offsets[b], offsets[b + 1]), the layout nconv_backproject_points emits. Rows from
+ *            offsets[B] on (and below offsets[0]) are ignored. n_rows is a host value and sizes the
+ *            grid; the offsets are never read on the host.
+ *   m        fp32 row-major 3x4 projection of image b at m + b * m_image_stride, read on the device;
+ *            m_image_stride = 0: one camera for the whole batch.
+ * Per point p = (x, y, z), with a row r = (r0, r1, r2, r3) of m,
+ *     dot(r, p) = ((r0 * x + r1 * y) + r2 * z) + r3
+ * each operation one fp32 rounding in that order (no FMA), and
+ *     a = dot(m[0], p), b = dot(m[1], p), c = dot(m[2], p),  u = a / c, v = b / c  (IEEE division),
+ *     fj = rintf(u), fi = rintf(v)                                               (ties to even).
+ * The point is valid iff
+ *     c > z_min && c <= z_max && fj >= 0 && fj <= W - 1 && fi >= 0 && fi <= H - 1
+ * all float comparisons made before any integer conversion, so NaN, +-inf and huge coordinates are
+ * simply not valid. z_min must be >= 0; z_max = 0 means FLT_MAX, as in nconv_backproject.
+ * Outputs:
+ *   depth    (B, 1, H, W) contiguous fp32, overwritten entirely: depth[b][0][i][j] = the minimum c
+ *            over the valid points of image b that land on (i, j), 0.0f where none lands.
+ *   index    optional (B, H, W) int32: the row number in `points` of the winning point, -1 where the
+ *            pixel is empty; among points with bit-equal c on one pixel the smallest row number wins.
+ * Both are functions of the input alone: identical on every run, whatever order the hardware
+ * executes in (an integer minimum over the bit pattern of c, which is positive and so orders as an
+ * unsigned integer).
+ * (the struct tag shares its name with the entry point, as nconv_frame_ingest's does: spell the type
+ * `struct nconv_lidar_project` or nconv_lidar_project_desc) */
+typedef struct nconv_lidar_project {
+    int B, H, W;
+    int point_stride;          /* floats per row, >= 3                                          */
+    const float* points;       /* may be NULL when n_rows == 0                                  */
+    long long n_rows;          /* rows in points, 0 <= n_rows < 2^31                            */
+    const int* offsets;        /* (B + 1) int32, on the device                                  */
+    const float* m;            /* (3, 4) or (B, 3, 4) fp32 row-major, on the device             */
+    long long m_image_stride;  /* floats; 0: one camera for the batch                           */
+    float z_min;               /* valid: c > z_min (>= 0)                                       */
+    float z_max;               /* ... && c <= z_max; 0: FLT_MAX                                 */
+} nconv_lidar_project_desc;
+
+/* Without index: 0 (the z-buffer is the output plane itself). With index: 8 * B * H * W bytes, a
+ * 64-bit key (bits(c) << 32 | row) per pixel. 0 for invalid sizes (B, H or W <= 0, B * H * W >= 2^31). */
+size_t nconv_lidar_project_workspace_bytes(int B, int H, int W, int with_index);
+
+/* Three kernels on `stream` (fill, scatter, resolve), no host synchronisation, no allocation, no
+ * waiting between workgroups. index NULL: the workspace is not used. Otherwise workspace must hold
+ * nconv_lidar_project_workspace_bytes(B, H, W, 1) bytes, 8-byte aligned; it is overwritten. depth and
+ * index are 4-byte aligned. n_rows == 0 is legal: an all-zero plane, index all -1. -EINVAL before any
+ * launch for a NULL descriptor / points (with n_rows > 0) / offsets / m / depth, B, H or W <= 0,
+ * B * H * W >= 2^31, n_rows < 0 or >= 2^31, point_stride < 3 or > 2^20, m_image_stride < 0, z_min < 0
+ * or NaN, z_max < z_min with z_max != 0 (or NaN), a workspace that is NULL, short or misaligned beside
+ * an index, misaligned points, offsets, m, depth or index. */
+int nconv_lidar_project(const struct nconv_lidar_project* d, float* depth, int* index, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

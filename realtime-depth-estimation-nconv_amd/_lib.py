@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NCONV_LIB: an alternative build of the same library (kernel-tuning experiments)
 LIB_PATH = os.environ.get("NCONV_LIB") or os.path.join(_HERE, "libnconv.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 BWD_ACCUMULATE = 1
 BWD_DEFER_REDUCE = 2
 BWD_SEPARATE = 4  # accepted and ignored since ABI 21 (include/nconv.h)
@@ -80,6 +80,8 @@ EXPORTED = (
     "nconv_backproject_map",
     "nconv_backproject_workspace_bytes",
     "nconv_backproject_points",
+    "nconv_lidar_project_workspace_bytes",
+    "nconv_lidar_project",
 )
 
 
@@ -158,6 +160,13 @@ class NconvBackproject(ctypes.Structure):
                 ("color_channel_stride", ctypes.c_longlong), ("color_row_stride", ctypes.c_longlong),
                 ("reverse", ctypes.c_int), ("z_min", ctypes.c_float), ("z_max", ctypes.c_float),
                 ("conf_min", ctypes.c_float), ("k", ctypes.c_void_p), ("k_image_stride", ctypes.c_longlong)]
+
+
+class NconvLidarProject(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("point_stride", ctypes.c_int),
+                ("points", ctypes.c_void_p), ("n_rows", ctypes.c_longlong), ("offsets", ctypes.c_void_p),
+                ("m", ctypes.c_void_p), ("m_image_stride", ctypes.c_longlong), ("z_min", ctypes.c_float),
+                ("z_max", ctypes.c_float)]
 
 
 _lib = None
@@ -260,6 +269,10 @@ def _declare(lib):
     lib.nconv_backproject_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_backproject_points.restype = I
     lib.nconv_backproject_points.argtypes = [ctypes.POINTER(NconvBackproject), P, P, P, L, P, P, ctypes.c_size_t, P]
+    lib.nconv_lidar_project_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_lidar_project_workspace_bytes.argtypes = [I, I, I, I]
+    lib.nconv_lidar_project.restype = I
+    lib.nconv_lidar_project.argtypes = [ctypes.POINTER(NconvLidarProject), P, P, P, ctypes.c_size_t, P]
 
 
 def lib():

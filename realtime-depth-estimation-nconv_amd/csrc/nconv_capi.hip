@@ -838,4 +838,45 @@ int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned ch
     return rc ? fail(rc, fn, why) : 0;
 }
 
+size_t nconv_lidar_project_workspace_bytes(int B, int H, int W, int with_index) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return with_index ? (size_t)8 * B * H * W : 0;
+}
+
+int nconv_lidar_project(const struct nconv_lidar_project* d, float* depth, int* index, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_lidar_project";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)d->B * d->H * d->W >= (1LL << 31))
+        return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->n_rows < 0 || d->n_rows >= (1LL << 31)) return fail(-22, fn, "n_rows must be in [0, 2^31)");
+    if (d->point_stride < 3 || d->point_stride > (1 << 20))
+        return fail(-22, fn, "point_stride must be in [3, 2^20]");
+    if (!d->points && d->n_rows > 0) return fail(-22, fn, "null points");
+    if (!d->offsets || !d->m) return fail(-22, fn, "null offsets or m");
+    if (!depth) return fail(-22, fn, "null depth");
+    if (d->m_image_stride < 0) return fail(-22, fn, "negative m image stride");
+    if (!(d->z_min >= 0.f)) return fail(-22, fn, "z_min must be >= 0 (and not NaN)");
+    const float z_max = d->z_max == 0.f ? __FLT_MAX__ : d->z_max;
+    if (!(z_max >= d->z_min)) return fail(-22, fn, "z_max < z_min (or NaN)");
+    if ((size_t)d->points % 4 || (size_t)d->offsets % 4 || (size_t)d->m % 4 || (size_t)depth % 4 || (size_t)index % 4)
+        return fail(-22, fn, "points / offsets / m / depth / index not 4-byte aligned");
+    if (index) {
+        if (!workspace || workspace_bytes < nconv_lidar_project_workspace_bytes(d->B, d->H, d->W, 1))
+            return fail(-22, fn, "workspace too small");
+        if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    }
+    nconv::LidarArgs a{};
+    a.B = d->B, a.H = d->H, a.W = d->W;
+    a.n_rows = (int)d->n_rows, a.stride = d->point_stride;
+    a.vec = d->point_stride == 4 && (size_t)d->points % 16 == 0;
+    a.points = d->points, a.offsets = d->offsets, a.m = d->m, a.mbs = d->m_image_stride;
+    a.z_min = d->z_min, a.z_max = z_max;
+    const char* why = nullptr;
+    int rc = nconv::launch_lidar_project(a, depth, index, index ? (unsigned long long*)workspace : nullptr,
+                                         (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

@@ -295,4 +295,20 @@ int launch_backproject_map(const BackprojectArgs& a, float* xyz, hipStream_t st,
 int launch_backproject_points(const BackprojectArgs& a, float* xyz, unsigned char* rgb, int* index, int capacity,
                               int* offsets, int* ws, hipStream_t st, const char** why);
 
+// Projection of a LiDAR scan to the sparse depth plane (nconv_lidar_project), lidar_project.hip.
+struct LidarArgs {
+    int B, H, W;
+    int n_rows;            // rows of points (< 2^31)
+    int stride;            // floats per row (3 .. 2^20)
+    int vec;               // stride == 4 and a 16-byte aligned base: 128-bit row loads
+    const float* points;
+    const int* offsets;    // (B + 1), on the device
+    const float* m;
+    long long mbs;         // image stride of m in floats (0: one camera)
+    float z_min, z_max;
+};
+// keys: null = the 32-bit z-buffer in `depth` itself; else B * H * W 64-bit keys (index is written too)
+int launch_lidar_project(const LidarArgs& a, float* depth, int* index, unsigned long long* keys, hipStream_t st,
+                         const char** why);
+
 }  // namespace nconv
