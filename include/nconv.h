@@ -508,9 +508,12 @@ int nconv_relu_bias_bwd(int B, int C, int H, int W, const float* g, const float*
  * the workspace, which nconv_depth_loss_bwd reads: g (contiguous B x H x W, OVERWRITTEN) =
  * gloss[0] * dL/dr (gloss NULL: 1). Deterministic (fixed-order reductions). */
 size_t nconv_depth_loss_workspace_bytes(int B, int H, int W);
+/* -EINVAL "plane too large" where an operand's extent ((H - 1) * row stride + W) * 4 reaches 2^31
+ * bytes (a plane is read through 32-bit byte offsets), like the other entry points that take views. */
 int nconv_depth_loss_fwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* The same checks as the forward, the 2^31-byte extent limit ("plane too large") included. */
 int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          const float* gloss, const void* workspace, size_t workspace_bytes, float* g, void* stream);

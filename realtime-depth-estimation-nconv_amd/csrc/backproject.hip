@@ -13,12 +13,10 @@
 // cy = K[0][0], K[1][1], K[0][2], K[1][2] of image b's 3 x 3 matrix, read here (the other entries
 // are not read).
 //
-// As in frame_io.hip a wave of 64 lanes takes four consecutive pixels per lane: one wave owns a
-// segment of 256 consecutive pixels of one image row, a block of four waves four segments. Sources
-// are read through buffer resources sized to the view's exact extent: 128-bit loads of 4 fp32 (96-bit
-// of 4 interleaved RGB pixels) where base and strides are aligned and the four pixels lie inside the
-// row, element-wide otherwise; a lane with nothing to read aims past the resource (kOOB) and gets 0.
-// No load touches memory outside the views.
+// A wave of 64 lanes takes four consecutive pixels per lane: one wave owns a segment of 256
+// consecutive pixels of one image row, a block of four waves four segments. Depth, confidence and
+// colour are views read with plane_io.h's loaders (load4_f32, load4_rgb8); a lane with nothing to
+// read passes n = 0 and gets 0. No load touches memory outside the views.
 //
 // Compaction: `count` writes each segment's number of valid pixels (four 64-bit ballots, popcount) to
 // the workspace; `scan` (one workgroup looping over the array) turns them in place into exclusive
@@ -34,14 +32,10 @@ namespace nconv {
 
 namespace {
 
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBT = 256;                // threads: four waves, one segment each
 constexpr int kSeg = 64 * 4;            // pixels per segment (four per lane)
 constexpr int kScanT = 1024;            // the scan's single workgroup
 constexpr int kScanE = 4;               // segments per thread and round
-constexpr unsigned kOOB = 0x80000000u;  // past every resource (extents are < 2^31 bytes): reads 0
 
 struct Camera {
     float fx, fy, cx, cy;
@@ -64,32 +58,24 @@ __device__ __forceinline__ bool segment_of_wave(const BackprojectArgs& a, Where&
     return true;
 }
 
-// values k (bits of `want`, all below n) of the four fp32 at byte offset off; the others read 0
-__device__ __forceinline__ f4 row_load4(__amdgpu_buffer_rsrc_t r, bool vec, int n, unsigned want, unsigned off) {
-    if (vec && (n == 4 || want == 0u))
-        return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, want ? off : kOOB, 0, 0));
-    f4 v;
-    v.x = ld_f32(r, want & 1u ? off : kOOB);
-    v.y = ld_f32(r, want & 2u ? off + 4u : kOOB);
-    v.z = ld_f32(r, want & 4u ? off + 8u : kOOB);
-    v.w = ld_f32(r, want & 8u ? off + 12u : kOOB);
-    return v;
+// the four fp32 of view v at the wave's place (its row is inside the plane), the leading n of them
+// (<= 0: none); the others read 0
+__device__ __forceinline__ f4 view_load4(const BackprojectArgs& a, const PlaneView& v, const float* image,
+                                         const Where& w, int n) {
+    const __amdgpu_buffer_rsrc_t r = plane_rsrc(image, view_bytes(a.H, v.rs, a.W, 4));
+    return load4_f32(r, v.wide != 0, true, n, (unsigned)((long long)w.i * v.rs + w.j) * 4u);
 }
 
 // bit k: pixel j + k of row i is valid; z = the four depths (0 past the row)
 __device__ __forceinline__ unsigned valid4(const BackprojectArgs& a, const Where& w, f4& z) {
     const unsigned in_row = w.n > 0 ? (1u << w.n) - 1u : 0u;
-    const int dbytes = (int)(((long long)(a.H - 1) * a.drs + a.W) * 4);
-    const __amdgpu_buffer_rsrc_t rd = plane_rsrc(a.depth + (long long)w.b * a.dbs, dbytes);
-    z = row_load4(rd, a.d_vec != 0, w.n, in_row, (unsigned)((long long)w.i * a.drs + w.j) * 4u);
+    z = view_load4(a, a.depth, a.depth.image<float>(w.b), w, w.n);
     unsigned m = 0u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) m |= (unsigned)(z[k] > a.z_min && z[k] <= a.z_max) << k;
     m &= in_row;
-    if (a.conf) {
-        const int cbytes = (int)(((long long)(a.H - 1) * a.crs + a.W) * 4);
-        const __amdgpu_buffer_rsrc_t rc = plane_rsrc(a.conf + (long long)w.b * a.cbs, cbytes);
-        const f4 c = row_load4(rc, a.c_vec != 0, w.n, in_row, (unsigned)((long long)w.i * a.crs + w.j) * 4u);
+    if (a.conf.base) {
+        const f4 c = view_load4(a, a.conf, a.conf.image<float>(w.b), w, w.n);
         unsigned mc = 0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k) mc |= (unsigned)(c[k] >= a.conf_min) << k;
@@ -123,34 +109,20 @@ __device__ __forceinline__ unsigned colour_q(float v) {
 // c[k] = the three output bytes of pixel k (byte 0 first) for the pixels in `want`
 __device__ __forceinline__ void colour4(const BackprojectArgs& a, const Where& w, unsigned want, unsigned (&c)[4]) {
     c[0] = c[1] = c[2] = c[3] = 0u;
+    const int n = want ? w.n : 0;  // the row's pixels where the lane stores any of them, else nothing
     if (a.color_kind == NCONV_COLOR_F32_PLANAR) {
-        const float* base = (const float*)a.color + (long long)w.b * a.obs;
-        const int bytes = (int)(((long long)(a.H - 1) * a.ors + a.W) * 4);
-        const unsigned off = (unsigned)((long long)w.i * a.ors + w.j) * 4u;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const __amdgpu_buffer_rsrc_t r = plane_rsrc(base + (long long)ch * a.ocs, bytes);
-            const f4 v = row_load4(r, a.o_fast != 0, w.n, want, off);
+            const f4 v = view_load4(a, a.color, a.color.image<float>(w.b) + (long long)ch * a.ocs, w, n);
             const int sh = 8 * (a.reverse ? 2 - ch : ch);
 #pragma unroll
             for (int k = 0; k < 4; ++k) c[k] |= colour_q(v[k]) << sh;
         }
     } else {
-        const unsigned char* base = (const unsigned char*)a.color + (long long)w.b * a.obs;
-        const int bytes = (int)((long long)(a.H - 1) * a.ors + 3LL * a.W);
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, bytes, 0x00020000);
-        const unsigned off = (unsigned)((long long)w.i * a.ors + 3LL * w.j);
-        unsigned d[3] = {0u, 0u, 0u};
-        if (a.o_fast && (w.n == 4 || want == 0u)) {
-            const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(r, want ? off : kOOB, 0, 0);
-            d[0] = v.x, d[1] = v.y, d[2] = v.z;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 12; ++q) {
-                const unsigned byte = __builtin_amdgcn_raw_buffer_load_b8(r, (want >> (q / 3)) & 1u ? off + q : kOOB, 0, 0);
-                d[q >> 2] |= (byte & 0xffu) << ((q & 3) * 8);
-            }
-        }
+        const __amdgpu_buffer_rsrc_t r =
+            bytes_rsrc(a.color.image<unsigned char>(w.b), view_bytes(a.H, a.color.rs, 3LL * a.W, 1));
+        unsigned d[3];
+        load4_rgb8(r, a.color.wide != 0, true, n, (unsigned)((long long)w.i * a.color.rs + 3LL * w.j), d);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -159,18 +131,6 @@ __device__ __forceinline__ void colour4(const BackprojectArgs& a, const Where& w
                 c[k] |= ((d[q >> 2] >> ((q & 3) * 8)) & 0xffu) << (8 * (a.reverse ? 2 - ch : ch));
             }
     }
-}
-
-// n (0..4) leading values of v to p[0..n): one 128-bit store where p is 16-byte aligned
-__device__ __forceinline__ void put4(float* p, f4 v, int n) {
-    if (n == 4 && ((size_t)p & 15) == 0) {
-        *(f4*)p = v;
-        return;
-    }
-    if (n > 0) p[0] = v.x;
-    if (n > 1) p[1] = v.y;
-    if (n > 2) p[2] = v.z;
-    if (n > 3) p[3] = v.w;
 }
 
 // lanes below this one that have their bit set in the ballot
@@ -197,9 +157,9 @@ __global__ __launch_bounds__(kBT) void backproject_map(BackprojectArgs a, float*
     }
     const size_t plane = (size_t)a.H * a.W;
     float* p = xyz + (size_t)w.b * 3 * plane + (size_t)w.i * a.W + w.j;
-    put4(p, x, w.n);
-    put4(p + plane, y, w.n);
-    put4(p + 2 * plane, z, w.n);
+    store4_f32(p, x, w.n);
+    store4_f32(p + plane, y, w.n);
+    store4_f32(p + 2 * plane, z, w.n);
 }
 
 __global__ __launch_bounds__(kBT) void backproject_count(BackprojectArgs a, int* __restrict__ counts) {
@@ -299,15 +259,6 @@ __global__ __launch_bounds__(kBT) void backproject_write(BackprojectArgs a, cons
         if (index) index[rank] = pix + k;
         ++rank;
     }
-}
-
-int launch_status(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
 }
 
 }  // namespace

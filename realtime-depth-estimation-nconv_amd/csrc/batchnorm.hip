@@ -358,12 +358,7 @@ int launch_relu_bias_bwd(int B, int C, int H, int W, const float* g, const float
     hipLaunchKernelGGL(relu_bias_stats, dim3(ncp, C, B), dim3(kBT), 0, st, g, out, gm, C, hw, ncp, nparts, vec, ws);
     if (gbias)
         hipLaunchKernelGGL(channel_sum_finalize, dim3(C), dim3(kBT), 0, st, ws, C, nparts, gbias);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -387,12 +382,7 @@ int launch_bn_train_fwd(const nconv_bn_train& p, float* ws, hipStream_t st, cons
     const int vy = vec && ((uintptr_t)p.y % 16 == 0);
     hipLaunchKernelGGL(bn_apply, dim3(ncp, p.C, p.B), dim3(kBT), 0, st, p.x, p.y, p.C, hw, vy, p.mean, p.invstd,
                        p.gamma, p.beta, p.relu);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 int launch_bn_train_bwd(const nconv_bn_train& p, const float* gy, float* gx, float* ggamma, float* gbeta, float* ws,
@@ -407,12 +397,7 @@ int launch_bn_train_bwd(const nconv_bn_train& p, const float* gy, float* gx, flo
     if (gx)
         hipLaunchKernelGGL(bn_bwd_apply, dim3(ncp, p.C, p.B), dim3(kBT), 0, st, gy, p.x, gx, p.C, hw,
                            vec && ((uintptr_t)gx % 16 == 0), p.mean, p.invstd, p.gamma, p.beta, p.relu, sums);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 }  // namespace nconv

@@ -9,13 +9,10 @@
 //
 // Both work on tiles of 8 rows x 256 pixels: a wave per pair of rows, four consecutive pixels per
 // lane, so a wave's stores of one row are one contiguous span (1 KB of fp32 per channel, 512 B of
-// uint16) and its loads of one row likewise (768 B of RGB). As in metrics.hip the sources are read
-// through a buffer resource sized to the image's exact extent, wide where the base and strides are
-// aligned and the four pixels lie inside the row, element-wide range-checked loads otherwise: a
-// 96-bit load of 4 RGB pixels / a 64-bit load of 4 uint16 / a dword of 4 uint8 (base and strides
-// 4-byte aligned), a 128-bit load of 4 fp32 (16-byte aligned). No load touches a byte outside
-// [base, base + (h-1) * row stride + w * element): a wide load is issued only when all its bytes
-// are inside a row, everything else goes byte by byte (short by short, dword by dword).
+// uint16) and its loads of one row likewise (768 B of RGB). The sources are views read as plane_io.h
+// describes, RGB and fp32 with its loaders; plane_load4 here follows the same rule for the integer
+// planes: a 64-bit load of 4 uint16 / a dword of 4 uint8 where base and strides are 4-byte aligned
+// and the four pixels lie inside the row, short by short (byte by byte) otherwise.
 // Outputs are 128-bit (ingest) / 64-bit (export) stores where the four pixels' address is aligned,
 // else per-element (export: aligned pairs as dwords, single uint16 at the row edges).
 // No LDS, no atomics, no host synchronisation, no allocation.
@@ -24,37 +21,17 @@
 namespace nconv {
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kIT = 256;             // threads: four waves
 constexpr int kIR = 2;               // rows per wave
 constexpr int kIH = kIT / 64 * kIR;  // rows per tile
 constexpr int kIW = 64 * 4;          // pixels per tile row (four per lane)
-constexpr unsigned kOOB = 0x80000000u;  // past every resource (extents are < 2^31 bytes): reads 0
 
 static int frame_tiles_per_image(int H, int W) { return ((H + kIH - 1) / kIH) * ((W + kIW - 1) / kIW); }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bytes_rsrc(const void* p, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, bytes, 0x00020000);
-}
-__device__ __forceinline__ unsigned ld_u8(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
-}
 __device__ __forceinline__ unsigned ld_u16(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
-}
-
-// n (0..4) leading values of v to p[0..n): one 128-bit store where p is 16-byte aligned
-__device__ __forceinline__ void store4(float* p, f4 v, int n) {
-    if (n == 4 && ((size_t)p & 15) == 0) {
-        *(f4*)p = v;
-        return;
-    }
-    if (n > 0) p[0] = v.x;
-    if (n > 1) p[1] = v.y;
-    if (n > 2) p[2] = v.z;
-    if (n > 3) p[3] = v.w;
 }
 
 // byte k (0..11) of three dwords as a float: v_cvt_f32_ubyte{0..3}
@@ -64,24 +41,13 @@ __device__ __forceinline__ float byte_f32(const unsigned (&d)[3], int k) {
 
 // rows i0 .. i0 + kIR - 1, pixels j .. j + 3 of image b's RGB
 __device__ __forceinline__ void ingest_rgb(const IngestArgs& a, int b, int i0, int j) {
-    const unsigned char* base = a.rgb + (long long)b * a.rgb_bs;
-    const __amdgpu_buffer_rsrc_t r = bytes_rsrc(base, (int)((long long)(a.h - 1) * a.rgb_rs + 3LL * a.w));
+    const __amdgpu_buffer_rsrc_t r = bytes_rsrc(a.rgb.image<unsigned char>(b), view_bytes(a.h, a.rgb.rs, 3LL * a.w, 1));
     const int n = min(4, a.w - j);  // <= 0: the lane is past the row
     unsigned d[kIR][3];
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
         const int i = i0 + rr;
-        const bool row_in = i < a.h;
-        const unsigned off = (unsigned)((long long)i * a.rgb_rs + 3LL * j);
-        if (a.rgb_fast && (!row_in || n == 4 || n <= 0)) {
-            const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(r, row_in && n == 4 ? off : kOOB, 0, 0);
-            d[rr][0] = v.x, d[rr][1] = v.y, d[rr][2] = v.z;
-        } else {
-            d[rr][0] = d[rr][1] = d[rr][2] = 0u;
-#pragma unroll
-            for (int k = 0; k < 12; ++k)
-                d[rr][k >> 2] |= ld_u8(r, row_in && k < 3 * n ? off + k : kOOB) << ((k & 3) * 8);
-        }
+        load4_rgb8(r, a.rgb.wide != 0, i < a.h, n, (unsigned)((long long)i * a.rgb.rs + 3LL * j), d[rr]);
     }
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
@@ -91,52 +57,49 @@ __device__ __forceinline__ void ingest_rgb(const IngestArgs& a, int b, int i0, i
         for (int c = 0; c < 3; ++c) {
             const f4 v = {byte_f32(d[rr], c), byte_f32(d[rr], 3 + c), byte_f32(d[rr], 6 + c), byte_f32(d[rr], 9 + c)};
             const int oc = a.reverse ? 2 - c : c;
-            store4(a.rgb_out + (((size_t)b * 3 + oc) * a.h + i) * a.w + j, v, n);
+            store4_f32(a.rgb_out + (((size_t)b * 3 + oc) * a.h + i) * a.w + j, v, n);
         }
     }
 }
 
-// four values of a plane row as unsigned integers (U8 / U16) or fp32 bits (F32); off = byte offset of pixel j
+// four values of a plane row as unsigned integers (U8 / U16) or fp32 bits (F32); off = byte offset of
+// pixel j; in_row and n as plane_io.h's loaders take them
 template <int DT>
-__device__ __forceinline__ u32x4 plane_load4(__amdgpu_buffer_rsrc_t r, bool fast, bool row_in, int n, unsigned off) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (fast && (!row_in || n == 4 || n <= 0)) {
-        const unsigned o = row_in && n == 4 ? off : kOOB;
+__device__ __forceinline__ u32x4 plane_load4(__amdgpu_buffer_rsrc_t r, bool wide, bool in_row, int n, unsigned off) {
+    if (DT == NCONV_FRAME_F32) return __builtin_bit_cast(u32x4, load4_f32(r, wide, in_row, n, off));
+    u32x4 v;
+    if (wide && (!in_row || n == 4 || n <= 0)) {
+        const unsigned o = in_row && n == 4 ? off : kOOB;
         if (DT == NCONV_FRAME_U8) {
             const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0);
             v.x = w & 0xffu, v.y = (w >> 8) & 0xffu, v.z = (w >> 16) & 0xffu, v.w = w >> 24;
-        } else if (DT == NCONV_FRAME_U16) {
+        } else {
             const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, o, 0, 0);
             v.x = w.x & 0xffffu, v.y = w.x >> 16, v.z = w.y & 0xffffu, v.w = w.y >> 16;
-        } else {
-            v = __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0);
         }
         return v;
     }
-    constexpr unsigned E = DT == NCONV_FRAME_U8 ? 1u : DT == NCONV_FRAME_U16 ? 2u : 4u;
-    unsigned e[4];
+    constexpr unsigned E = DT == NCONV_FRAME_U8 ? 1u : 2u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const unsigned o = row_in && k < n ? off + E * k : kOOB;
-        e[k] = DT == NCONV_FRAME_U8 ? ld_u8(r, o)
-               : DT == NCONV_FRAME_U16 ? ld_u16(r, o)
-                                       : (unsigned)__builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0);
+        const unsigned o = in_row && k < n ? off + E * k : kOOB;
+        v[k] = DT == NCONV_FRAME_U8 ? ld_u8(r, o) : ld_u16(r, o);
     }
-    v.x = e[0], v.y = e[1], v.z = e[2], v.w = e[3];
     return v;
 }
 
 template <int DT>
 __device__ __forceinline__ void ingest_plane(const IngestArgs& a, const IngestPlane& p, int b, int i0, int j) {
     constexpr int E = DT == NCONV_FRAME_U8 ? 1 : DT == NCONV_FRAME_U16 ? 2 : 4;
-    const unsigned char* base = p.src + (long long)b * p.bs;
-    const __amdgpu_buffer_rsrc_t r = bytes_rsrc(base, (int)((long long)(a.h - 1) * p.rs + (long long)E * a.w));
+    const __amdgpu_buffer_rsrc_t r =
+        bytes_rsrc(p.src.image<unsigned char>(b), view_bytes(a.h, p.src.rs, (long long)E * a.w, 1));
     const int n = min(4, a.w - j);
     u32x4 v[kIR];
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
         const int i = i0 + rr;
-        v[rr] = plane_load4<DT>(r, p.fast != 0, i < a.h, n, (unsigned)((long long)i * p.rs + (long long)E * j));
+        const unsigned off = (unsigned)((long long)i * p.src.rs + (long long)E * j);
+        v[rr] = plane_load4<DT>(r, p.src.wide != 0, i < a.h, n, off);
     }
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
@@ -149,7 +112,7 @@ __device__ __forceinline__ void ingest_plane(const IngestArgs& a, const IngestPl
             const u32x4 s = v[rr] >> (unsigned)p.shift;
             f = f4{(float)s.x, (float)s.y, (float)s.z, (float)s.w} * p.scale;
         }
-        store4(p.out + ((size_t)b * a.h + i) * a.w + j, f, n);
+        store4_f32(p.out + ((size_t)b * a.h + i) * a.w + j, f, n);
     }
 }
 
@@ -192,23 +155,13 @@ __global__ __launch_bounds__(kIT) void depth_export(ExportArgs a) {
     const int ntw = (a.W + kIW - 1) / kIW, per = ntw * ((a.H + kIH - 1) / kIH);
     const int b = blockIdx.x / per, t = blockIdx.x - b * per;
     const int i0 = (t / ntw) * kIH + (threadIdx.x >> 6) * kIR, j = (t % ntw) * kIW + (threadIdx.x & 63) * 4;
-    const float* base = a.d + (long long)b * a.bs;
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc(base, (int)(((long long)(a.H - 1) * a.rs + a.W) * 4));
+    const __amdgpu_buffer_rsrc_t r = plane_rsrc(a.d.image<float>(b), view_bytes(a.H, a.d.rs, a.W, 4));
     const int n = min(4, a.W - j);
     f4 v[kIR];
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
         const int i = i0 + rr;
-        const bool row_in = i < a.H;
-        const unsigned off = (unsigned)((long long)i * a.rs + j) * 4u;
-        if (a.vec && (!row_in || n == 4 || n <= 0)) {
-            v[rr] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, row_in && n == 4 ? off : kOOB, 0, 0));
-        } else {
-            v[rr].x = ld_f32(r, row_in && n > 0 ? off : kOOB);
-            v[rr].y = ld_f32(r, row_in && n > 1 ? off + 4u : kOOB);
-            v[rr].z = ld_f32(r, row_in && n > 2 ? off + 8u : kOOB);
-            v[rr].w = ld_f32(r, row_in && n > 3 ? off + 12u : kOOB);
-        }
+        v[rr] = load4_f32(r, a.d.wide != 0, i < a.H, n, (unsigned)((long long)i * a.d.rs + j) * 4u);
     }
 #pragma unroll
     for (int rr = 0; rr < kIR; ++rr) {
@@ -230,20 +183,11 @@ __global__ __launch_bounds__(kIT) void depth_export(ExportArgs a) {
     }
 }
 
-static int launch_status(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
-}
-
 int launch_frame_ingest(const IngestArgs& a, hipStream_t st, const char** why) {
     int jobs[3] = {0, 0, 0}, nj = 0;
-    if (a.rgb) jobs[nj++] = 0;
-    if (a.pl[0].src) jobs[nj++] = 1;
-    if (a.pl[1].src) jobs[nj++] = 2;
+    if (a.rgb.base) jobs[nj++] = 0;
+    if (a.pl[0].src.base) jobs[nj++] = 1;
+    if (a.pl[1].src.base) jobs[nj++] = 2;
     hipLaunchKernelGGL(frame_ingest, dim3(a.B * frame_tiles_per_image(a.h, a.w), nj), dim3(kIT), 0, st, a, jobs[0],
                        jobs[1], jobs[2]);
     return launch_status(why);

@@ -24,7 +24,7 @@
 // A block takes 256 consecutive rows and reads them through a buffer resource over exactly its rows'
 // extent (the last row ends after its third float): 128-bit loads of whole 4-float rows where the
 // stride is 4 and the base 16-byte aligned, the last row of the scan excepted (its fourth float is
-// past the extent), element loads otherwise. A lane without a row aims past the resource and reads 0.
+// past the extent), element loads otherwise. A lane without a row aims at plane_io.h's kOOB and reads 0.
 // The image of a row comes from a binary search of offsets, staged in LDS up to kLdsOffsets entries
 // and read from global memory above that. A wave whose first and last rows are in the same image
 // (almost every wave) takes the matrix from wave-uniform addresses, which the compiler turns into
@@ -46,7 +46,6 @@ typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kT = 256;                 // threads of every kernel here; rows of a scatter block
 constexpr int kLdsOffsets = 1024;       // offsets are staged in LDS up to this many entries (B + 1)
-constexpr unsigned kOOB = 0x80000000u;  // past every resource (extents are < 2^31 bytes): reads 0
 constexpr unsigned kEmpty32 = 0xFFFFFFFFu;
 constexpr unsigned long long kEmpty64 = ~0ull;
 
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(kT) void lidar_scatter(LidarArgs a, float wmax, flo
 
     // x, y, z through a resource over this block's rows alone (its extent is below 2^31 bytes): whole
     // rows where a later block's row follows, else up to the third float of the scan's last row
-    const int bytes = r0 + nb < a.n_rows ? nb * a.stride * 4 : ((nb - 1) * a.stride + 3) * 4;
+    const int bytes = view_bytes(nb, a.stride, r0 + nb < a.n_rows ? a.stride : 3, 4);
     const __amdgpu_buffer_rsrc_t rs = plane_rsrc(a.points + (size_t)r0 * a.stride, bytes);
     float x, y, z;
     if (a.vec && (t + 1) * 16 <= bytes) {
@@ -262,15 +261,6 @@ __global__ __launch_bounds__(kT) void lidar_scatter(LidarArgs a, float wmax, flo
         const Matrix q = matrix_at(a.m + (long long)(in ? b : 0) * a.mbs);
         scatter_point<KEYS>(a, wmax, hmax, q, in ? b : 0, in, row, x, y, z, zbuf, keys);
     }
-}
-
-int launch_status(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
 }
 
 // the largest float <= n (n >= 0): n itself where it is a float, else the float below

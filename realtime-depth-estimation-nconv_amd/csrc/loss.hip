@@ -18,7 +18,8 @@
 //   loss_grad      per tile: the signs of gx, gy over the tile + 1-pixel halo into LDS, then
 //                  dL/dr = go m [c_e e - c_g sum_q (sign gx(q) Kx(p - q) + sign gy(q) Ky(p - q))]
 //                  over the 3x3 neighbours q inside the plane, with torch's sign(0) = 0 for |.|'.
-// Deterministic (no atomics). The planes may be row-strided views (the cropped DNET output).
+// Deterministic (no atomics). The planes may be row-strided views (the cropped DNET output): the
+// views of plane_io.h, read here element by element over the halo window (extent and kOOB as there).
 #include "nconv_internal.h"
 
 namespace nconv {
@@ -87,17 +88,16 @@ __device__ __forceinline__ LossTile loss_tile(const LossPlane& p) {
 // so no load waits on another), then diff = t - masked_fill(r, t == 0, 0).
 __device__ __forceinline__ void stage_diff(const LossPlane& p, int i0, int j0, float* dw) {
     constexpr int NS = (kDH * kDW + kLT - 1) / kLT;
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rt = plane_rsrc(p.t, (int)(((long long)(p.H - 1) * p.ts + p.W) * 4));
-    const __amdgpu_buffer_rsrc_t rr = plane_rsrc(p.r, (int)(((long long)(p.H - 1) * p.rs + p.W) * 4));
+    const __amdgpu_buffer_rsrc_t rt = plane_rsrc(p.t, view_bytes(p.H, p.ts, p.W, 4));
+    const __amdgpu_buffer_rsrc_t rr = plane_rsrc(p.r, view_bytes(p.H, p.rs, p.W, 4));
     float tv[NS], rv[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
         const int e = threadIdx.x + kLT * k;
         const int a = e / kDW, c = e - a * kDW, i = i0 - 2 + a, j = j0 - 2 + c;
         const bool in = e < kDH * kDW && (unsigned)i < (unsigned)p.H && (unsigned)j < (unsigned)p.W;
-        tv[k] = ld_f32(rt, in ? (unsigned)(i * p.ts + j) * 4u : OOB);
-        rv[k] = ld_f32(rr, in ? (unsigned)(i * p.rs + j) * 4u : OOB);
+        tv[k] = ld_f32(rt, in ? (unsigned)(i * p.ts + j) * 4u : kOOB);
+        rv[k] = ld_f32(rr, in ? (unsigned)(i * p.rs + j) * 4u : kOOB);
     }
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -242,30 +242,25 @@ static int loss_tiles(int B, int H, int W) { return B * ((H + kTH - 1) / kTH) * 
 
 size_t loss_workspace_bytes(int B, int H, int W) { return (3 * (size_t)loss_tiles(B, H, W) + 4) * sizeof(float); }
 
-static int loss_err(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+static LossPlane loss_plane(const LossArgs& a) {
+    return LossPlane{(const float*)a.r.base, (const float*)a.t.base, a.r.rs, a.t.rs, a.r.bs, a.t.bs, a.B, a.H, a.W};
 }
 
 int launch_loss_fwd(const LossArgs& a, int grad_loss, float* loss, float* ws, hipStream_t st, const char** why) {
-    const LossPlane p{a.r, a.t, a.rs, a.ts, a.rbs, a.tbs, a.B, a.H, a.W};
+    const LossPlane p = loss_plane(a);
     const int nblk = loss_tiles(a.B, a.H, a.W);
     float* coef = ws;
     float* part = ws + 4;
     hipLaunchKernelGGL(loss_partials, dim3(nblk), dim3(kLT), 0, st, p, grad_loss, part);
     hipLaunchKernelGGL(loss_finalize, dim3(1), dim3(kLT), 0, st, part, nblk, a.B * a.H * a.W, grad_loss, loss, coef);
-    return loss_err(why);
+    return launch_status(why);
 }
 
 int launch_loss_bwd(const LossArgs& a, int grad_loss, const float* gout, const float* ws, float* g, hipStream_t st,
                     const char** why) {
-    const LossPlane p{a.r, a.t, a.rs, a.ts, a.rbs, a.tbs, a.B, a.H, a.W};
+    const LossPlane p = loss_plane(a);
     hipLaunchKernelGGL(loss_grad, dim3(loss_tiles(a.B, a.H, a.W)), dim3(kLT), 0, st, p, grad_loss, ws, gout, g);
-    return loss_err(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

@@ -8,8 +8,8 @@
 //           7 sum(1/p - 1/g)^2  8 sum(ln p - ln g)^2  9-11 #{max(p/g, g/p) < 1.25, 1.25^2, 1.25^3}
 //
 // In PyTorch these are ~40 elementwise / reduction launches per frame; here, on the loss's 16 x 64
-// pixel tiles (four consecutive pixels of a row per thread, one 128-bit load per operand where its
-// base and strides are 16-byte aligned, four range-checked dword loads otherwise):
+// pixel tiles (four consecutive pixels of a row per thread, read from the two views with plane_io.h's
+// load4_f32):
 //   metrics_partials  one workgroup per tile of one image: the per-pixel terms in fp32 (IEEE division,
 //                     logf, no contraction), twelve fp32 tile partials (counts <= 1024 are exact)
 //   metrics_finalize  one block of sixteen waves: a wave per image sums its tiles in a fixed order in
@@ -25,21 +25,6 @@ constexpr int kMH = 16, kMW = 64;  // pixel tile of one workgroup (4 consecutive
 constexpr int kNS = NCONV_DEPTH_METRICS_SUMS;
 
 static int metrics_tiles_per_image(int H, int W) { return ((H + kMH - 1) / kMH) * ((W + kMW - 1) / kMW); }
-
-// Four consecutive pixels (row i, columns j .. j+3) of a plane through its buffer resource; pixels
-// outside the plane read 0 (an invalid target). off = the byte offset of (i, j).
-__device__ __forceinline__ f4 metrics_load4(__amdgpu_buffer_rsrc_t r, bool vec, bool row_in, int j, int W,
-                                            unsigned off) {
-    constexpr unsigned OOB = 0x80000000u;
-    if (vec && (!row_in || j + 3 < W))
-        return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, row_in ? off : OOB, 0, 0));
-    f4 v;
-    v.x = ld_f32(r, row_in && j < W ? off : OOB);
-    v.y = ld_f32(r, row_in && j + 1 < W ? off + 4u : OOB);
-    v.z = ld_f32(r, row_in && j + 2 < W ? off + 8u : OOB);
-    v.w = ld_f32(r, row_in && j + 3 < W ? off + 12u : OOB);
-    return v;
-}
 
 // one pixel's terms added to the thread's twelve sums
 __device__ __forceinline__ void metrics_pixel(float pr, float g, const MetricsArgs& a, float (&s)[kNS]) {
@@ -73,13 +58,12 @@ __global__ __launch_bounds__(kMT) void metrics_partials(MetricsArgs a, float* __
     const int ntw = (a.W + kMW - 1) / kMW, nth = (a.H + kMH - 1) / kMH;
     const int b = blockIdx.x / (ntw * nth), t = blockIdx.x - b * ntw * nth;
     const int i = (t / ntw) * kMH + (threadIdx.x >> 4), j = (t % ntw) * kMW + (threadIdx.x & 15) * 4;
-    const float* pp = a.p + (long long)b * a.pbs;
-    const float* gp = a.g + (long long)b * a.gbs;
-    const __amdgpu_buffer_rsrc_t rp = plane_rsrc(pp, (int)(((long long)(a.H - 1) * a.prs + a.W) * 4));
-    const __amdgpu_buffer_rsrc_t rg = plane_rsrc(gp, (int)(((long long)(a.H - 1) * a.grs + a.W) * 4));
-    const bool row_in = i < a.H;
-    const f4 pv = metrics_load4(rp, a.p_vec != 0, row_in, j, a.W, (unsigned)((long long)i * a.prs + j) * 4u);
-    const f4 gv = metrics_load4(rg, a.g_vec != 0, row_in, j, a.W, (unsigned)((long long)i * a.grs + j) * 4u);
+    const __amdgpu_buffer_rsrc_t rp = plane_rsrc(a.p.image<float>(b), view_bytes(a.H, a.p.rs, a.W, 4));
+    const __amdgpu_buffer_rsrc_t rg = plane_rsrc(a.g.image<float>(b), view_bytes(a.H, a.g.rs, a.W, 4));
+    const bool row_in = i < a.H;  // pixels outside the plane read 0 (an invalid target)
+    const int n = min(4, a.W - j);
+    const f4 pv = load4_f32(rp, a.p.wide != 0, row_in, n, (unsigned)((long long)i * a.p.rs + j) * 4u);
+    const f4 gv = load4_f32(rg, a.g.wide != 0, row_in, n, (unsigned)((long long)i * a.g.rs + j) * 4u);
     float s[kNS];
 #pragma unroll
     for (int k = 0; k < kNS; ++k) s[k] = 0.f;
@@ -150,12 +134,7 @@ int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, 
     float* part = (float*)(img + (size_t)a.B * kNS);
     hipLaunchKernelGGL(metrics_partials, dim3(a.B * tiles), dim3(kMT), 0, st, a, part);
     hipLaunchKernelGGL(metrics_finalize, dim3(1), dim3(kFT), 0, st, part, a.B, tiles, img, sums, accum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 }  // namespace nconv

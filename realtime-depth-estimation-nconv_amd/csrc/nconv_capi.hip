@@ -93,6 +93,34 @@ const char* validate_bn(const nconv_bn_train* p) {
     return nullptr;
 }
 
+// The three reasons a view can be refused, in one entry point's wording.
+struct ViewText {
+    const char *row, *large, *image;
+};
+constexpr ViewText kViewHW{"row stride smaller than W", "plane too large", "image stride smaller than H * row stride"};
+constexpr ViewText kViewBytes{"row stride smaller than the row's bytes", "plane too large",
+                              "image stride smaller than h * row stride"};
+constexpr ViewText kViewPoints{"row stride smaller than W", "plane too large: extent of 2^31 bytes or more",
+                               "image stride smaller than H * row stride"};
+constexpr long long kNoStrideLimit = 0x7fffffffffffffffLL;
+
+// One view of B planes of H rows of `row` elements of `elem` bytes, strides bs / rs in elements, checked
+// and turned into the kernels' PlaneView (plane_io.h): NULL, or the reason it is refused. A view's byte
+// offsets inside one image are 32-bit (buffer loads) and kOOB must lie past it, so its extent stays
+// below 2^31 bytes; `limit` is the entry point's own, older bound on H * rs * elem (kNoStrideLimit:
+// the extent alone). The image offsets are 64-bit. `align`: what base and strides must be multiples of,
+// in bytes, for the wide loads.
+const char* view_args(const void* base, int B, int H, long long row, long long elem, long long bs, long long rs,
+                      long long limit, long long align, const ViewText& t, nconv::PlaneView& v) {
+    if (rs < row) return t.row;
+    const long long cap = (1LL << 31) / elem;
+    if (rs >= limit / elem / H || row >= cap || (H > 1 && rs > (cap - 1 - row) / (H - 1))) return t.large;
+    if (B > 1 && bs < H * rs) return t.image;
+    v.base = base, v.bs = B > 1 ? bs : 0, v.rs = rs;
+    v.wide = (size_t)base % align == 0 && v.rs % (align / elem) == 0 && v.bs % (align / elem) == 0;
+    return nullptr;
+}
+
 LayerDev make_dev(const nconv_layer* L) {
     LayerDev d;
     d.L = *L;
@@ -445,10 +473,9 @@ int nconv_wgrad_reduce_ex(int n, const nconv_layer* layers, void* const* workspa
     }
     if (m == 0) return 0;
     const char* why = nullptr;
-    const int rc = nconv::launch_wgrad_reduce_multi(m, jobs, (hipStream_t)stream, &why);
-    if (rc) return fail(rc, fn, why);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(-5, fn, hipGetErrorString(e));
+    int rc = nconv::launch_wgrad_reduce_multi(m, jobs, (hipStream_t)stream, &why);
+    if (!rc) rc = launch_status(&why);
+    return rc ? fail(rc, fn, why) : 0;
 }
 
 size_t nconv_dense_packed_floats(int kind, int Cin, int Cout) {
@@ -596,13 +623,16 @@ size_t nconv_depth_loss_workspace_bytes(int B, int H, int W) {
     return nconv::loss_workspace_bytes(B, H, W);
 }
 
-static const char* validate_loss(const nconv::LossArgs& a, size_t ws_bytes, const void* ws) {
-    if (!a.r || !a.t) return "null plane";
-    if (a.B <= 0 || a.H <= 0 || a.W <= 0) return "non-positive B/H/W";
-    if ((long long)a.B * a.H * a.W > (1LL << 30)) return "batch too large";
-    if (a.rs < a.W || a.ts < a.W) return "row stride smaller than W";
-    if (a.B > 1 && (a.rbs < a.H * a.rs || a.tbs < a.H * a.ts)) return "image stride smaller than H * row stride";
-    if (!ws || ws_bytes < nconv::loss_workspace_bytes(a.B, a.H, a.W)) return "workspace too small";
+// The planes of nconv_depth_loss_fwd / _bwd checked and turned into the kernels' arguments.
+static const char* loss_args(const float* r, long long rbs, long long rrs, const float* t, long long tbs,
+                             long long trs, int B, int H, int W, size_t ws_bytes, const void* ws, nconv::LossArgs& a) {
+    if (!r || !t) return "null plane";
+    if (B <= 0 || H <= 0 || W <= 0) return "non-positive B/H/W";
+    if ((long long)B * H * W > (1LL << 30)) return "batch too large";
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(r, B, H, W, 4, rbs, rrs, kNoStrideLimit, 16, kViewHW, a.r)) return why;
+    if (const char* why = view_args(t, B, H, W, 4, tbs, trs, kNoStrideLimit, 16, kViewHW, a.t)) return why;
+    if (!ws || ws_bytes < nconv::loss_workspace_bytes(B, H, W)) return "workspace too small";
     return nullptr;
 }
 
@@ -610,8 +640,10 @@ int nconv_depth_loss_fwd(const float* r, long long r_image_stride, long long r_r
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          float* loss, void* workspace, size_t workspace_bytes, void* stream) {
     const char* fn = "nconv_depth_loss_fwd";
-    const nconv::LossArgs a{r, t, r_image_stride, r_row_stride, t_image_stride, t_row_stride, B, H, W};
-    if (const char* why = validate_loss(a, workspace_bytes, workspace)) return fail(-22, fn, why);
+    nconv::LossArgs a;
+    if (const char* why = loss_args(r, r_image_stride, r_row_stride, t, t_image_stride, t_row_stride, B, H, W,
+                                    workspace_bytes, workspace, a))
+        return fail(-22, fn, why);
     if (!loss) return fail(-22, fn, "null loss");
     const char* why = nullptr;
     int rc = nconv::launch_loss_fwd(a, use_gradient_loss != 0, loss, (float*)workspace, (hipStream_t)stream, &why);
@@ -622,8 +654,10 @@ int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_r
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          const float* gloss, const void* workspace, size_t workspace_bytes, float* g, void* stream) {
     const char* fn = "nconv_depth_loss_bwd";
-    const nconv::LossArgs a{r, t, r_image_stride, r_row_stride, t_image_stride, t_row_stride, B, H, W};
-    if (const char* why = validate_loss(a, workspace_bytes, workspace)) return fail(-22, fn, why);
+    nconv::LossArgs a;
+    if (const char* why = loss_args(r, r_image_stride, r_row_stride, t, t_image_stride, t_row_stride, B, H, W,
+                                    workspace_bytes, workspace, a))
+        return fail(-22, fn, why);
     if (!g) return fail(-22, fn, "null g");
     const char* why = nullptr;
     int rc = nconv::launch_loss_bwd(a, use_gradient_loss != 0, gloss, (const float*)workspace, g, (hipStream_t)stream,
@@ -645,11 +679,12 @@ int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p
     if (!sums && !accum) return fail(-22, fn, "null sums and accum");
     if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
     if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
-    if (p_row_stride < W || g_row_stride < W) return fail(-22, fn, "row stride smaller than W");
-    // a plane's byte offsets are 32-bit (buffer loads); the image offsets are 64-bit
-    if (p_row_stride >= (1LL << 29) / H || g_row_stride >= (1LL << 29) / H) return fail(-22, fn, "plane too large");
-    if (B > 1 && (p_image_stride < H * p_row_stride || g_image_stride < H * g_row_stride))
-        return fail(-22, fn, "image stride smaller than H * row stride");
+    nconv::MetricsArgs a;
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(pred, B, H, W, 4, p_image_stride, p_row_stride, 1LL << 31, 16, kViewHW, a.p))
+        return fail(-22, fn, why);
+    if (const char* why = view_args(gt, B, H, W, 4, g_image_stride, g_row_stride, 1LL << 31, 16, kViewHW, a.g))
+        return fail(-22, fn, why);
     if (!(gt_min >= 0.f) || !(gt_max >= 0.f) || !(clamp_lo >= 0.f) || !(clamp_hi >= 0.f))
         return fail(-22, fn, "negative or NaN bound");
     if (gt_min > 0.f && gt_max > 0.f && gt_min > gt_max) return fail(-22, fn, "gt_min > gt_max");
@@ -658,14 +693,9 @@ int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p
         return fail(-22, fn, "workspace too small");
     if ((size_t)workspace % 8 || (size_t)sums % 8 || (size_t)accum % 8)
         return fail(-22, fn, "workspace / sums / accum not 8-byte aligned");
-    auto vec = [&](const float* q, long long bs, long long rs) {
-        return (size_t)q % 16 == 0 && rs % 4 == 0 && (B == 1 || bs % 4 == 0);
-    };
     const float inf = __builtin_inff();
-    const nconv::MetricsArgs a{pred, gt, B > 1 ? p_image_stride : 0, p_row_stride, B > 1 ? g_image_stride : 0,
-                               g_row_stride, B, H, W, vec(pred, p_image_stride, p_row_stride),
-                               vec(gt, g_image_stride, g_row_stride), gt_min, gt_max > 0.f ? gt_max : inf,
-                               clamp_lo > 0.f ? clamp_lo : -inf, clamp_hi > 0.f ? clamp_hi : inf};
+    a.g_lo = gt_min, a.g_hi = gt_max > 0.f ? gt_max : inf;
+    a.c_lo = clamp_lo > 0.f ? clamp_lo : -inf, a.c_hi = clamp_hi > 0.f ? clamp_hi : inf;
     const char* why = nullptr;
     int rc = nconv::launch_metrics(a, sums, accum, workspace, (hipStream_t)stream, &why);
     return rc ? fail(rc, fn, why) : 0;
@@ -678,22 +708,19 @@ int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream) {
     if (d->B <= 0 || d->h <= 0 || d->w <= 0) return fail(-22, fn, "non-positive B/h/w");
     if ((long long)d->B * d->h * d->w > (1LL << 30)) return fail(-22, fn, "batch too large");
     const int B = d->B, h = d->h, w = d->w;
-    // a view's byte offsets inside one image are 32-bit (buffer loads); the image offsets are 64-bit
-    auto view = [&](long long bs, long long rs, long long row_bytes) -> const char* {
-        if (rs < row_bytes) return "row stride smaller than the row's bytes";
-        if (rs >= (1LL << 30) / h) return "plane too large";
-        if (B > 1 && bs < h * rs) return "image stride smaller than h * row stride";
-        return nullptr;
+    // views in bytes (rows of row_bytes one-byte elements), extents below 2^30 bytes
+    auto view = [&](const void* base, long long bs, long long rs, long long row_bytes, long long align,
+                    nconv::PlaneView& v) {
+        return view_args(base, B, h, row_bytes, 1, bs, rs, 1LL << 30, align, kViewBytes, v);
     };
     nconv::IngestArgs a{};
     a.B = B, a.h = h, a.w = w, a.reverse = d->reverse != 0;
     if (d->rgb) {
-        if (const char* why = view(d->rgb_image_stride, d->rgb_row_stride, 3LL * w)) return fail(-22, fn, why);
+        if (const char* why = view(d->rgb, d->rgb_image_stride, d->rgb_row_stride, 3LL * w, 4, a.rgb))
+            return fail(-22, fn, why);
         if (!d->rgb_out) return fail(-22, fn, "null rgb_out");
         if ((size_t)d->rgb_out % 4) return fail(-22, fn, "rgb_out not 4-byte aligned");
-        a.rgb = d->rgb, a.rgb_bs = B > 1 ? d->rgb_image_stride : 0, a.rgb_rs = d->rgb_row_stride;
         a.rgb_out = d->rgb_out;
-        a.rgb_fast = (size_t)a.rgb % 4 == 0 && a.rgb_rs % 4 == 0 && a.rgb_bs % 4 == 0;
     }
     for (int k = 0; k < 2; ++k) {
         const nconv_frame_plane& p = d->plane[k];
@@ -703,15 +730,14 @@ int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream) {
         const long long E = p.dtype == NCONV_FRAME_U8 ? 1 : p.dtype == NCONV_FRAME_U16 ? 2 : 4;
         if (p.shift < 0 || p.shift > 15) return fail(-22, fn, "shift outside 0..15");
         if (p.dtype == NCONV_FRAME_F32 && p.shift != 0) return fail(-22, fn, "non-zero shift with F32");
-        if (const char* why = view(p.image_stride, p.row_stride, E * w)) return fail(-22, fn, why);
-        const long long bs = B > 1 ? p.image_stride : 0;
-        if ((size_t)p.src % E || p.row_stride % E || bs % E)
+        nconv::IngestPlane& q = a.pl[k];
+        const long long A = p.dtype == NCONV_FRAME_F32 ? 16 : 4;
+        if (const char* why = view(p.src, p.image_stride, p.row_stride, E * w, A, q.src)) return fail(-22, fn, why);
+        if ((size_t)p.src % E || q.src.rs % E || q.src.bs % E)
             return fail(-22, fn, "U16 / F32 plane not aligned to its element size");
         if (!p.out) return fail(-22, fn, "null plane out");
         if ((size_t)p.out % 4) return fail(-22, fn, "plane out not 4-byte aligned");
-        const long long A = p.dtype == NCONV_FRAME_F32 ? 16 : 4;
-        a.pl[k] = nconv::IngestPlane{(const unsigned char*)p.src, bs, p.row_stride, p.out, p.dtype, p.shift, p.scale,
-                                     (size_t)p.src % A == 0 && p.row_stride % A == 0 && bs % A == 0};
+        q.out = p.out, q.dtype = p.dtype, q.shift = p.shift, q.scale = p.scale;
     }
     const char* why = nullptr;
     int rc = nconv::launch_frame_ingest(a, (hipStream_t)stream, &why);
@@ -724,14 +750,12 @@ int nconv_depth_export_u16(const float* pred, long long image_stride, long long 
     if (!pred || !out) return fail(-22, fn, "null pred or out");
     if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
     if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
-    if (row_stride < W) return fail(-22, fn, "row stride smaller than W");
-    if (row_stride >= (1LL << 29) / H) return fail(-22, fn, "plane too large");
-    if (B > 1 && image_stride < H * row_stride) return fail(-22, fn, "image stride smaller than H * row stride");
+    nconv::ExportArgs a;
+    a.B = B, a.H = H, a.W = W, a.scale = scale, a.out = out;
+    if (const char* why = view_args(pred, B, H, W, 4, image_stride, row_stride, 1LL << 31, 16, kViewHW, a.d))
+        return fail(-22, fn, why);
     if (!(scale > 0.f) || scale == __builtin_inff()) return fail(-22, fn, "scale must be positive and finite");
     if ((size_t)pred % 4 || (size_t)out % 2) return fail(-22, fn, "pred not 4-byte or out not 2-byte aligned");
-    const long long bs = B > 1 ? image_stride : 0;
-    const nconv::ExportArgs a{pred, bs, row_stride, B, H, W, (size_t)pred % 16 == 0 && row_stride % 4 == 0 && bs % 4 == 0,
-                              scale, out};
     const char* why = nullptr;
     int rc = nconv::launch_depth_export(a, (hipStream_t)stream, &why);
     return rc ? fail(rc, fn, why) : 0;
@@ -751,27 +775,18 @@ static const char* backproject_args(const nconv_backproject* d, bool with_color,
     const float z_max = d->z_max == 0.f && d->z_min >= 0.f ? __FLT_MAX__ : d->z_max;
     if (!(z_max >= d->z_min)) return "z_max < z_min (or NaN)";
     if (d->conf_min != d->conf_min) return "conf_min is NaN";
-    // a view's byte offsets inside one image are 32-bit (buffer loads); the image offsets are 64-bit
-    auto view = [&](long long bs, long long rs, long long row, long long elem) -> const char* {
-        if (rs < row) return "row stride smaller than W";
-        if (rs >= (1LL << 31) / elem / H) return "plane too large: extent of 2^31 bytes or more";
-        if (B > 1 && bs < H * rs) return "image stride smaller than H * row stride";
-        return nullptr;
-    };
-    auto vec = [&](const void* q, long long bs, long long rs) {
-        return (size_t)q % 16 == 0 && rs % 4 == 0 && (B == 1 || bs % 4 == 0);
+    // fp32 planes of W elements (128-bit loads), or interleaved bytes (96-bit loads, 4-byte alignment)
+    auto view = [&](const void* base, long long bs, long long rs, bool f32, nconv::PlaneView& v) {
+        return f32 ? view_args(base, B, H, W, 4, bs, rs, 1LL << 31, 16, kViewPoints, v)
+                   : view_args(base, B, H, 3LL * W, 1, bs, rs, 1LL << 31, 4, kViewPoints, v);
     };
     a = nconv::BackprojectArgs{};
     a.B = B, a.H = H, a.W = W, a.nseg = (int)nconv::backproject_segments(B, H, W);
-    if (const char* why = view(d->depth_image_stride, d->depth_row_stride, W, 4)) return why;
+    if (const char* why = view(d->depth, d->depth_image_stride, d->depth_row_stride, true, a.depth)) return why;
     if ((size_t)d->depth % 4 || (size_t)d->k % 4) return "depth or k not 4-byte aligned";
-    a.depth = d->depth, a.dbs = B > 1 ? d->depth_image_stride : 0, a.drs = d->depth_row_stride;
-    a.d_vec = vec(d->depth, a.dbs, a.drs);
     if (d->conf) {
-        if (const char* why = view(d->conf_image_stride, d->conf_row_stride, W, 4)) return why;
+        if (const char* why = view(d->conf, d->conf_image_stride, d->conf_row_stride, true, a.conf)) return why;
         if ((size_t)d->conf % 4) return "conf not 4-byte aligned";
-        a.conf = d->conf, a.cbs = B > 1 ? d->conf_image_stride : 0, a.crs = d->conf_row_stride;
-        a.c_vec = vec(d->conf, a.cbs, a.crs);
     }
     if (d->color_kind != NCONV_COLOR_NONE && d->color_kind != NCONV_COLOR_F32_PLANAR &&
         d->color_kind != NCONV_COLOR_U8_INTERLEAVED)
@@ -779,19 +794,16 @@ static const char* backproject_args(const nconv_backproject* d, bool with_color,
     if ((d->color != nullptr) != (d->color_kind != NCONV_COLOR_NONE)) return "color and color_kind: both or neither";
     if (with_color) {
         if (!d->color) return "rgb output without a color source";
-        a.color = d->color, a.color_kind = d->color_kind, a.reverse = d->reverse != 0;
-        a.obs = B > 1 ? d->color_image_stride : 0, a.ors = d->color_row_stride;
-        if (d->color_kind == NCONV_COLOR_F32_PLANAR) {
-            if (const char* why = view(d->color_image_stride, d->color_row_stride, W, 4)) return why;
+        a.color_kind = d->color_kind, a.reverse = d->reverse != 0;
+        const bool planar = d->color_kind == NCONV_COLOR_F32_PLANAR;
+        if (const char* why = view(d->color, d->color_image_stride, d->color_row_stride, planar, a.color)) return why;
+        if (planar) {
             if (d->color_channel_stride < H * d->color_row_stride) return "channel stride smaller than H * row stride";
             if (B > 1 && d->color_image_stride < 2 * d->color_channel_stride + H * d->color_row_stride)
                 return "image stride smaller than H * row stride";
             if ((size_t)d->color % 4) return "color not 4-byte aligned";
             a.ocs = d->color_channel_stride;
-            a.o_fast = vec(d->color, a.obs, a.ors) && a.ocs % 4 == 0;
-        } else {
-            if (const char* why = view(d->color_image_stride, d->color_row_stride, 3LL * W, 1)) return why;
-            a.o_fast = (size_t)d->color % 4 == 0 && a.ors % 4 == 0 && a.obs % 4 == 0;
+            a.color.wide = a.color.wide && a.ocs % 4 == 0;
         }
     }
     a.k = d->k, a.kbs = d->k_image_stride;

@@ -13,9 +13,9 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/nconv.h"
+#include "plane_io.h"  // f4, kOOB, plane_rsrc, ld_f32, launch_status
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // Layer descriptor as the kernels see it: the C-ABI struct plus host-derived constants.
 struct LayerDev {
@@ -340,15 +340,9 @@ __device__ __forceinline__ void stage_plane(const LayerDev& d, const ChanSrc& s,
 // Elements are dealt to the NTH threads in row-major order, so consecutive lanes read consecutive
 // columns; slots past the tile go to a dump slot after the plane (PLANE_STRIDE).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const float* p, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, bytes, 0x00020000);
-}
-
-__device__ __forceinline__ float ld_f32(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-// with a wave-uniform byte offset in soffset (a plane of a multi-plane resource); the range check
-// covers voffset + soffset, so an out-of-range voffset (>= 2^31) still reads 0
+// plane_rsrc and ld_f32 are plane_io.h's. ld_f32 with a wave-uniform byte offset in soffset (a plane
+// of a multi-plane resource); the range check covers voffset + soffset, so an out-of-range voffset
+// (>= 2^31) still reads 0
 __device__ __forceinline__ float ld_f32s(__amdgpu_buffer_rsrc_t r, unsigned off, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, soff, 0));
 }
@@ -386,7 +380,7 @@ struct TileStager {
     static constexpr int PLANE = IHT * IWP;      // f2 slots of the plane ...
     static constexpr int PLANE_STRIDE = PLANE + 2;  // ... + the dump slot, 16-B aligned
     static constexpr bool UP = MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST;
-    static constexpr unsigned OOB = 0x80000000u;
+    static constexpr unsigned OOB = kOOB;
     unsigned lofs[NE];       // f2 slot in the plane
     unsigned ga[NE];         // byte offset in a source-a plane (POOL2: of the window's top-left)
     unsigned gb[UP ? NE : 1];  // byte offset in a source-b plane (nearest upsampling)
@@ -458,7 +452,7 @@ template <int MODE>
 __device__ __forceinline__ void load_px(const LayerDev& d, const ChanSrc& s, int ih, int iw, float& x, float& c) {
     const nconv_layer& L = d.L;
     const bool in = (unsigned)ih < (unsigned)L.H && (unsigned)iw < (unsigned)L.W;
-    constexpr unsigned OOB = 0x80000000u;
+    constexpr unsigned OOB = kOOB;
     const __amdgpu_buffer_rsrc_t rx = plane_rsrc(s.x, s.bytes);
     if constexpr (MODE == NCONV_LOAD_THRESH) {
         x = ld_f32(rx, in ? (unsigned)(ih * s.W + iw) * 4u : OOB);

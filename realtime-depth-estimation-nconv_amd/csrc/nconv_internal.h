@@ -215,12 +215,22 @@ int launch_relu_bias_bwd(int B, int C, int H, int W, const float* g, const float
 int launch_bn_train_bwd(const nconv_bn_train& p, const float* gy, float* gx, float* ggamma, float* gbeta, float* ws,
                         hipStream_t st, const char** why);
 
+// A batch of B planes of H rows as the I/O kernels read it (plane_io.h); checked and filled by
+// view_args in nconv_capi.hip. Strides are in the unit the owning struct states.
+struct PlaneView {
+    const void* base;
+    long long bs;  // image stride; 0 where B == 1
+    long long rs;  // row stride
+    int wide;      // base and strides keep every group of four pixels aligned for the wide loads
+    template <typename T>
+    __host__ __device__ const T* image(int b) const {
+        return (const T*)base + (long long)b * bs;
+    }
+};
+
 // Training loss (utils.py calculate_loss) on B planes.
 struct LossArgs {
-    const float* r;
-    const float* t;
-    long long rbs, rs;  // image / row strides of r (elements)
-    long long tbs, ts;  // ... of t
+    PlaneView r, t;  // fp32, strides in elements (wide is not used: the loss reads halo windows)
     int B, H, W;
 };
 size_t loss_workspace_bytes(int B, int H, int W);
@@ -230,12 +240,8 @@ int launch_loss_bwd(const LossArgs& a, int grad_loss, const float* gout, const f
 
 // Evaluation metrics (the twelve raw sums of nconv_depth_metrics) on B planes.
 struct MetricsArgs {
-    const float* p;
-    const float* g;
-    long long pbs, prs;  // image / row strides of the prediction (elements)
-    long long gbs, grs;  // ... of the target
+    PlaneView p, g;     // prediction and target: fp32, strides in elements
     int B, H, W;
-    int p_vec, g_vec;   // the operand's image bases and rows are 16-byte aligned: 128-bit loads
     float g_lo, g_hi;   // validity window of the target (absent bounds: 0, +inf)
     float c_lo, c_hi;   // clamp window of the prediction (absent bounds: -inf, +inf)
 };
@@ -244,29 +250,23 @@ int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, 
 
 // Raw frame ingest (nconv_frame_ingest) and 16-bit depth export (nconv_depth_export_u16), frame_io.hip.
 struct IngestPlane {
-    const unsigned char* src;  // null: absent
-    long long bs, rs;          // image / row strides in bytes
-    float* out;                // (B, 1, h, w) contiguous
-    int dtype, shift;          // enum nconv_frame_dtype; right shift of the integer value
+    PlaneView src;     // base null: absent; strides in bytes; wide: 4-byte aligned (F32: 16-byte)
+    float* out;        // (B, 1, h, w) contiguous
+    int dtype, shift;  // enum nconv_frame_dtype; right shift of the integer value
     float scale;
-    int fast;  // base and strides allow the wide loads (4-byte aligned; F32: 16-byte aligned)
 };
 struct IngestArgs {
     int B, h, w;
-    int reverse;               // RGB planes written in reverse channel order
-    const unsigned char* rgb;  // null: absent
-    long long rgb_bs, rgb_rs;  // bytes
-    float* rgb_out;            // (B, 3, h, w) contiguous
-    int rgb_fast;              // base and strides 4-byte aligned: 96-bit loads
+    int reverse;     // RGB planes written in reverse channel order
+    PlaneView rgb;   // base null: absent; uint8 interleaved, strides in bytes; wide: 4-byte aligned
+    float* rgb_out;  // (B, 3, h, w) contiguous
     IngestPlane pl[2];
 };
 int launch_frame_ingest(const IngestArgs& a, hipStream_t st, const char** why);
 
 struct ExportArgs {
-    const float* d;
-    long long bs, rs;  // image / row strides of d (elements)
+    PlaneView d;  // fp32, strides in elements
     int B, H, W;
-    int vec;           // d's image bases and rows are 16-byte aligned: 128-bit loads
     float scale;
     unsigned short* out;  // (B, 1, H, W) contiguous
 };
@@ -276,17 +276,13 @@ int launch_depth_export(const ExportArgs& a, hipStream_t st, const char** why);
 struct BackprojectArgs {
     int B, H, W;
     int nseg;                // B * H * ceil(W / 256) segments of 256 row pixels, one wave each
-    const float* depth;
-    long long dbs, drs;      // image / row strides of depth (elements)
-    const float* conf;       // null: no confidence gate
-    long long cbs, crs;
-    const void* color;       // null: none; else per color_kind
+    PlaneView depth;         // fp32, strides in elements
+    PlaneView conf;          // base null: no confidence gate; fp32, strides in elements
+    PlaneView color;         // base null: none; else per color_kind, strides in elements of its type
     int color_kind, reverse;
-    long long obs, ocs, ors; // image / channel / row strides of the colour (elements of its type)
+    long long ocs;           // channel stride of a planar colour (elements)
     const float* k;
     long long kbs;           // image stride of K in floats (0: one camera)
-    int d_vec, c_vec;        // image bases and rows 16-byte aligned: 128-bit loads
-    int o_fast;              // colour base and strides allow the wide loads (F32: 16-byte, U8: 4-byte)
     float z_min, z_max, conf_min;
 };
 long long backproject_segments(int B, int H, int W);

@@ -49,12 +49,7 @@ int launch_bilinear_ac(const float* x, int B, int C, int H, int W, float* y, int
     long long blocks = (n + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(bilinear_ac, dim3((unsigned)blocks), dim3(256), 0, st, x, H, W, y, Ho, Wo, sh, sw, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 }  // namespace nconv

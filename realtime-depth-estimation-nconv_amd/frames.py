@@ -17,25 +17,15 @@ import ctypes
 import numpy as np
 import torch
 
-from .train import _planes
+from . import _views
 
 # depth_decode -> (shift, scale) of an integer plane: data.imread_gray's two decodes, then / 256
 DECODES = {"reference": {torch.uint16: (8, 1.0 / 256.0), torch.uint8: (0, 1.0 / 256.0)},
            "kitti16": {torch.uint16: (0, 1.0 / 256.0), torch.uint8: (0, 1.0 / 256.0)}}
 
 
-def _typed_tensor(x, what, dtypes):
-    if not torch.is_tensor(x):
-        raise TypeError(f"frames: {what} must be a tensor, got {type(x).__name__}")
-    if x.dtype not in dtypes:
-        raise TypeError(f"frames: {what}: expected {' / '.join(str(d) for d in dtypes)}, got {x.dtype}")
-    return x
-
-
 def _on_device(x, what):
-    if not x.is_cuda:
-        raise RuntimeError(f"frames: {what} is on {x.device}; frames are converted by libnconv on ROCm devices only "
-                           "(no PyTorch fallback), move the tensors to the GPU")
+    _views.on_device(x, what, "frames", "frames are converted by libnconv")
 
 
 def _decode(depth_decode, dtype):
@@ -50,18 +40,13 @@ def _decode(depth_decode, dtype):
 
 def _rgb_view(x):
     """(B, h, w, image stride, row stride in bytes) of an interleaved uint8 (B, h, w, 3) view."""
-    _typed_tensor(x, "rgb", (torch.uint8,))
-    if x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"frames: rgb must be (B, h, w, 3), got {tuple(x.shape)}")
-    if x.stride(3) != 1 or x.stride(2) != 3:
-        raise ValueError(f"frames: rgb of strides {x.stride()} is not interleaved (unit innermost stride, pixel "
-                         "stride 3)")
-    return x.shape[0], x.shape[1], x.shape[2], x.stride(0), x.stride(1)
+    _views.require_tensor(x, "rgb", (torch.uint8,), "frames")
+    return _views.interleaved_u8_view(x, "rgb", "frames")
 
 
 def _plane_view(x, what):
     """(B, h, w, image stride, row stride in bytes) of a (B, h, w) or (B, 1, h, w) view."""
-    _typed_tensor(x, what, (torch.uint16, torch.uint8, torch.float32))
+    _views.require_tensor(x, what, (torch.uint16, torch.uint8, torch.float32), "frames")
     if x.dim() == 4 and x.shape[1] == 1:
         x = x[:, 0]
     if x.dim() != 3:
@@ -73,14 +58,7 @@ def _plane_view(x, what):
 
 
 def _output(out, key, shape, dtype, device):
-    t = None if out is None else out.get(key)
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise TypeError(f"frames: out[{key!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)}")
-    if t.device != device:
-        raise RuntimeError(f"frames: out[{key!r}] on {t.device}, the source on {device}")
-    return t
+    return _views.output(out, key, shape, dtype, device, "frames")
 
 
 def ingest(rgb=None, depth=None, gt=None, *, depth_decode="reference", reverse_rgb=True, out=None):
@@ -138,14 +116,9 @@ def export_depth16(pred, scale=256.0, out=None):
     NaN -> 0. pred: fp32 device tensor, (H, W), (1, H, W) or (B, 1, H, W) with unit-stride rows (a
     cropped view such as DNET's output works). scale = 256 is KITTI's format. One launch."""
     from . import _lib
-    _typed_tensor(pred, "pred", (torch.float32,))
-    g = _planes(pred)
-    if g is None:
-        raise ValueError(f"frames: pred of shape {tuple(pred.shape)} / strides {pred.stride()} is not an (H, W), "
-                         "(1, H, W) or (B, 1, H, W) set of unit-stride rows")
+    _views.require_tensor(pred, "pred", (torch.float32,), "frames")
+    B, H, W, bs, rs = _views.plane_view(pred, "pred", "frames")
     _on_device(pred, "pred")
-    B, bs, rs = g
-    H, W = pred.shape[-2], pred.shape[-1]
     res = _output(None if out is None else {"out": out}, "out", pred.shape, torch.uint16, pred.device)
     rc = _lib.lib().nconv_depth_export_u16(_lib.ptr(pred), bs, rs, B, H, W, float(scale), _lib.ptr(res),
                                            _lib.stream_handle(pred.device))

@@ -26,26 +26,18 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _views
 from .data import read_calib_file
 
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
 def _on_device(x, what):
-    if not x.is_cuda:
-        raise RuntimeError(f"lidar: {what} is on {x.device}; scans are projected by libnconv on ROCm devices only "
-                           "(no PyTorch fallback), move the tensors to the GPU")
+    _views.on_device(x, what, "lidar", "scans are projected by libnconv")
 
 
 def _output(out, key, shape, dtype, device):
-    t = None if out is None else out.get(key)
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise TypeError(f"lidar: out[{key!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)}")
-    if t.device != device:
-        raise RuntimeError(f"lidar: out[{key!r}] on {t.device}, the points on {device}")
-    return t
+    return _views.output(out, key, shape, dtype, device, "lidar", source="points")
 
 
 def _size(size):
@@ -79,10 +71,7 @@ def project_points(points, offsets, m, size, *, z_min=0.0, z_max=FLT_MAX, return
     'workspace' (uint8, workspace_bytes(B, H, W)). Three launches, no allocation when out is complete
     and offsets is a tensor, no host synchronisation."""
     from . import _lib
-    if not torch.is_tensor(points):
-        raise TypeError(f"lidar: points must be a tensor, got {type(points).__name__}")
-    if points.dtype != torch.float32:
-        raise TypeError(f"lidar: points: expected torch.float32, got {points.dtype}")
+    _views.require_tensor(points, "points", (torch.float32,), "lidar")
     if points.dim() != 2 or points.shape[1] < 3:
         raise ValueError(f"lidar: points must be (N, C >= 3), got {tuple(points.shape)}")
     N, C = points.shape
@@ -95,8 +84,7 @@ def project_points(points, offsets, m, size, *, z_min=0.0, z_max=FLT_MAX, return
     if offsets is None:
         offsets = [0, N]
     if torch.is_tensor(offsets):
-        if offsets.dtype != torch.int32:
-            raise TypeError(f"lidar: offsets: expected torch.int32, got {offsets.dtype}")
+        _views.require_tensor(offsets, "offsets", (torch.int32,), "lidar")
         if offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
             raise ValueError(f"lidar: offsets must be a contiguous (B + 1) vector, got {tuple(offsets.shape)}")
         B = offsets.numel() - 1
@@ -107,10 +95,7 @@ def project_points(points, offsets, m, size, *, z_min=0.0, z_max=FLT_MAX, return
         if any(b < a for a, b in zip(host, host[1:])) or host[0] < 0 or host[-1] > N:
             raise ValueError(f"lidar: offsets {host} must be non-decreasing inside [0, {N}]")
         B = len(host) - 1
-    if not torch.is_tensor(m):
-        raise TypeError(f"lidar: m must be a tensor, got {type(m).__name__}")
-    if m.dtype != torch.float32:
-        raise TypeError(f"lidar: m: expected torch.float32, got {m.dtype}")
+    _views.require_tensor(m, "m", (torch.float32,), "lidar")
     if tuple(m.shape) not in ((3, 4), (B, 3, 4)):
         raise ValueError(f"lidar: m must be (3, 4) or ({B}, 3, 4), got {tuple(m.shape)}")
     if not m.is_contiguous():

@@ -19,7 +19,7 @@ with g the target, p the (clamped) prediction, e = p - g, over the valid pixels 
 import torch
 import torch.distributed as dist
 
-from .train import _planes
+from . import _views
 
 NSUMS = 12
 # figures over the valid pixels (mean over n) and over the positive ones (mean over n_pos)
@@ -47,26 +47,18 @@ def _bounds(gt_min, gt_max, clamp):
 
 
 def _operand(x, what):
-    if not torch.is_tensor(x):
-        raise TypeError(f"depth metrics: {what} must be a tensor, got {type(x).__name__}")
-    if not x.is_cuda:
-        raise RuntimeError(f"depth metrics: {what} is on {x.device}; the sums are computed by libnconv on ROCm "
-                           "devices only (no PyTorch fallback), move the tensors to the GPU")
-    if x.dtype != torch.float32:
-        raise TypeError(f"depth metrics: {what}: expected float32, got {x.dtype}")
-    g = _planes(x)
-    if g is None:
-        raise ValueError(f"depth metrics: {what} of shape {tuple(x.shape)} / strides {x.stride()} is not an (H, W), "
-                         "(1, H, W) or (B, 1, H, W) set of unit-stride rows")
-    return g
+    """(B, H, W, image stride, row stride) of an fp32 device operand."""
+    if torch.is_tensor(x):  # a tensor's device is checked before its dtype
+        _views.on_device(x, what, "depth metrics", "the sums are computed by libnconv")
+    _views.require_tensor(x, what, (torch.float32,), "depth metrics", expected="float32")
+    return _views.plane_view(x, what, "depth metrics")
 
 
 def _launch(pred, gt, bounds, want_sums, accum):
     from . import _lib
-    B, pbs, prs = _operand(pred, "pred")
-    Bg, gbs, grs = _operand(gt, "gt")
-    H, W = pred.shape[-2], pred.shape[-1]
-    if B != Bg or (H, W) != (gt.shape[-2], gt.shape[-1]):
+    B, H, W, pbs, prs = _operand(pred, "pred")
+    Bg, Hg, Wg, gbs, grs = _operand(gt, "gt")
+    if (B, H, W) != (Bg, Hg, Wg):
         raise ValueError(f"depth metrics: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ")
     if pred.device != gt.device:
         raise RuntimeError(f"depth metrics: pred on {pred.device}, gt on {gt.device}")

@@ -20,33 +20,22 @@ import ctypes
 import numpy as np
 import torch
 
-from .train import _planes
+from . import _views
 
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
 def _on_device(x, what):
-    if not x.is_cuda:
-        raise RuntimeError(f"pointcloud: {what} is on {x.device}; points are computed by libnconv on ROCm devices "
-                           "only (no PyTorch fallback), move the tensors to the GPU")
+    _views.on_device(x, what, "pointcloud", "points are computed by libnconv")
 
 
 def _f32(x, what):
-    if not torch.is_tensor(x):
-        raise TypeError(f"pointcloud: {what} must be a tensor, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"pointcloud: {what}: expected torch.float32, got {x.dtype}")
-    return x
+    return _views.require_tensor(x, what, (torch.float32,), "pointcloud")
 
 
 def _plane_geometry(x, what):
     """(B, H, W, image stride, row stride) of an (H, W), (1, H, W) or (B, 1, H, W) fp32 view."""
-    _f32(x, what)
-    g = _planes(x)
-    if g is None:
-        raise ValueError(f"pointcloud: {what} of shape {tuple(x.shape)} / strides {x.stride()} is not an (H, W), "
-                         "(1, H, W) or (B, 1, H, W) set of unit-stride rows")
-    return g[0], x.shape[-2], x.shape[-1], g[1], g[2]
+    return _views.plane_view(_f32(x, what), what, "pointcloud")
 
 
 def _descriptor(depth, k, conf, conf_min, z_min, z_max):
@@ -98,15 +87,8 @@ def _color(d, color, reverse, geom, device):
         d.color_kind = _lib.COLOR_F32_PLANAR
         d.color_image_stride, d.color_channel_stride, d.color_row_stride = color.stride(0), color.stride(1), color.stride(2)
     elif color.dtype == torch.uint8:
-        if color.dim() == 3:
-            color = color[None]
-        if tuple(color.shape) != (B, H, W, 3):
-            raise ValueError(f"pointcloud: uint8 color must be ({B}, {H}, {W}, 3) interleaved, got {tuple(color.shape)}")
-        if color.stride(3) != 1 or color.stride(2) != 3:
-            raise ValueError(f"pointcloud: color of strides {color.stride()} is not interleaved (unit innermost "
-                             "stride, pixel stride 3)")
         d.color_kind = _lib.COLOR_U8_INTERLEAVED
-        d.color_image_stride, d.color_row_stride = color.stride(0), color.stride(1)
+        d.color_image_stride, d.color_row_stride = _views.interleaved_u8_view(color, "color", "pointcloud", geom)[3:]
     else:
         raise TypeError(f"pointcloud: color: expected torch.float32 planes or torch.uint8 interleaved, got {color.dtype}")
     _on_device(color, "color")
@@ -116,14 +98,7 @@ def _color(d, color, reverse, geom, device):
 
 
 def _output(out, key, shape, dtype, device):
-    t = None if out is None else out.get(key)
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise TypeError(f"pointcloud: out[{key!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)}")
-    if t.device != device:
-        raise RuntimeError(f"pointcloud: out[{key!r}] on {t.device}, the source on {device}")
-    return t
+    return _views.output(out, key, shape, dtype, device, "pointcloud")
 
 
 def backproject_map(depth, k, *, conf=None, conf_min=0.0, z_min=0.0, z_max=FLT_MAX, out=None):

@@ -49,9 +49,9 @@ def export_ref(d, scale=256.0):
 
 
 # ---- ingest sweep ------------------------------------------------------------------------------------
-INGEST_B = (1, 3)
+INGEST_B = (1, 2, 3)
 INGEST_H = (1, 3, 17)
-INGEST_W = (1, 5, 16, 17, 63, 64, 65, 130)
+INGEST_W = (1, 3, 4, 5, 16, 17, 63, 64, 65, 130, 255, 256, 257, 261)
 INGEST_LEFT = (0, 1, 2, 3, 5)
 PLANE_DTYPES = (np.uint16, np.uint8, np.float32)
 SPECIAL_U16 = (0, 255, 256, 65535)
@@ -74,9 +74,9 @@ def raw_allocation(rng, B, h, w, left, dtype, channels=None):
 
 
 # ---- export sweep ------------------------------------------------------------------------------------
-EXPORT_B = (1, 3)
-EXPORT_H = (1, 5)
-EXPORT_W = (1, 2, 3, 7, 8, 9, 64, 65)
+EXPORT_B = (1, 2, 3)
+EXPORT_H = (1, 5, 17)
+EXPORT_W = (1, 2, 3, 4, 5, 7, 8, 9, 64, 65, 255, 256, 257, 261)
 # exact ties (k + 0.5) / 256 for even and odd k, -0.0, negatives, above 255.998 (-> 65535), +-inf, NaN
 EXPORT_SPECIAL = np.array([(2 + 0.5) / 256, (3 + 0.5) / 256, (0 + 0.5) / 256, (1 + 0.5) / 256, (65534 + 0.5) / 256,
                            (65533 + 0.5) / 256, -0.0, -0.001, -3.5, -1e30, 255.9981, 255.999, 256.0, 300.0, 1e30,

@@ -13,9 +13,9 @@ FLT_MAX = float(np.finfo(np.float32).max)
 
 # the sweep: a row shorter than a lane's four pixels, the segment edges (256 pixels per wave), more
 # than two segments per row; one and several rows and images
-SWEEP_W = (1, 3, 4, 63, 255, 256, 257, 513)
+SWEEP_W = (1, 3, 4, 5, 63, 255, 256, 257, 261, 513)
 SWEEP_H = (1, 2, 9)
-SWEEP_B = (1, 3)
+SWEEP_B = (1, 2, 3)
 SWEEP_LEFT = (0, 1, 2, 3)  # first column of the view inside its allocation: every base alignment
 PATTERNS = ("none", "all", "p05", "p50", "holes", "special", "edges")
 INVALID = np.array([0.0, -0.0, -1.0, -80.0, np.nan, np.inf, -np.inf], dtype=F32)

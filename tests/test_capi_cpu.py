@@ -177,6 +177,38 @@ def test_depth_loss_validation_is_host_only(nconv_amd):
     assert torch.equal(got, nconv_amd.train._calculate_loss_torch(r, t, True))
 
 
+def test_depth_loss_rejects_a_plane_of_2_31_bytes(nconv_amd):
+    """A loss plane is read through 32-bit byte offsets, so a view whose extent
+    ((H - 1) * row stride + W) * 4 reaches 2^31 bytes is refused on the host, forward and backward,
+    for either operand; the largest extent below that passes the view checks (it gets as far as the
+    workspace check). No memory of that size is touched: nothing is launched."""
+    lib = nconv_amd._lib.lib()
+    p = ctypes.c_void_p(0x1000)
+    lim = 1 << 29  # elements in 2^31 bytes
+
+    def fwd(H, W, rrs, trs, ws_bytes):
+        rc = lib.nconv_depth_loss_fwd(p, 0, rrs, p, 0, trs, 1, H, W, 1, p, p, ws_bytes, None)
+        return rc, lib.nconv_last_error().decode()
+
+    def bwd(H, W, rrs, trs, ws_bytes):
+        rc = lib.nconv_depth_loss_bwd(p, 0, rrs, p, 0, trs, 1, H, W, 1, None, p, ws_bytes, p, None)
+        return rc, lib.nconv_last_error().decode()
+
+    for call in (fwd, bwd):
+        for H, W in ((2, 8), (5, 7), (352, 1216)):
+            over = -(-(lim - W) // (H - 1))  # the smallest row stride with (H - 1) * rs + W >= 2^29
+            assert (H - 1) * over + W >= lim > (H - 1) * (over - 1) + W
+            for rrs, trs in ((over, W), (W, over), (1 << 40, W)):
+                rc, err = call(H, W, rrs, trs, 1 << 20)
+                assert rc == -22 and "plane too large" in err, (call.__name__, H, W, rrs, trs, rc, err)
+            rc, err = call(H, W, over - 1, over - 1, 4)
+            assert rc == -22 and "workspace too small" in err, (call.__name__, H, W, rc, err)
+        rc, err = call(1, lim, lim, lim, 1 << 20)  # one row of 2^31 bytes
+        assert rc == -22 and "plane too large" in err, (call.__name__, rc, err)
+        rc, err = call(1, lim - 1, lim - 1, lim - 1, 4)
+        assert rc == -22 and "workspace too small" in err, (call.__name__, rc, err)
+
+
 def test_loss_plane_geometry(nconv_amd):
     """The batch geometry the fused loss accepts: (H, W), (1, H, W), (B, 1, H, W) incl. cropped views
     (row / image strides); several channels or a non-unit column stride are not loss planes."""

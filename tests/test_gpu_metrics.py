@@ -36,7 +36,14 @@ def _place(x, dev, layout):
 
 # the issue's cases, then aligned rows with a ragged last group of four (W % 4 != 0, row stride % 4 == 0)
 CASES = [(1, 1, 5, "plain"), (1, 7, 3, "plain"), (1, 16, 64, "plain"), (1, 17, 65, "plain"),
-         (3, 33, 130, "cropped"), (2, 352, 1216, "cropped"), (2, 18, 70, "padded")]
+         (3, 33, 130, "cropped"), (2, 352, 1216, "cropped"), (2, 18, 70, "padded"),
+         # the widths at which the shared loader (plane_io.h) changes path, on every alignment: image
+         # strides that are no multiple of 4 (B = 2 plain with odd H * W), bases one element off the
+         # 16-byte grid and row strides that are no multiple of 4 (cropped), aligned rows with a ragged
+         # last group (padded), fully aligned (plain with W % 4 == 0); H no multiple of the 16 tile rows
+         (2, 5, 1, "plain"), (2, 3, 3, "cropped"), (1, 9, 4, "plain"), (2, 4, 4, "cropped"), (1, 17, 5, "padded"),
+         (2, 17, 255, "padded"), (2, 3, 255, "plain"), (1, 20, 256, "plain"), (2, 18, 256, "cropped"),
+         (2, 5, 257, "plain"), (2, 17, 257, "padded"), (2, 17, 261, "padded"), (2, 3, 261, "cropped")]
 
 
 @pytest.mark.parametrize("B,H,W,layout", CASES)
