@@ -3,8 +3,11 @@ the training glue of nconv_amd.train (fused loss kernels on device tensors, the 
 optimizer factory and checkpoint format) and the validation loops, plus the KITTI loader names
 that utils.py re-exports (utils.py:1).
 
-save_depth writes the min-max normalised depth as an 8-bit PNG (the reference colours it with
-OpenCV's INFERNO map, utils.py:12-16; OpenCV is not available, so the image is grayscale).
+save_depth writes the min-max normalised depth as an 8-bit PNG. The reference colours it with
+OpenCV's INFERNO map (utils.py:12-16); a device tensor is coloured the same way on the device
+(nconv_amd.visualize.colorize: matplotlib's inferno colours times 255, rounded, which is how OpenCV's
+table is defined; OpenCV is not a dependency, so parity with cv2 itself is not pinned by a test). A
+host array without a cmap is written in grayscale, as it always was.
 """
 import os
 import sys
@@ -31,7 +34,20 @@ DepthMetrics = _m.metrics.DepthMetrics
 depth_metric_sums = _m.metrics.depth_metric_sums
 
 
-def save_depth(depth_data, path):
+def save_depth(depth_data, path, cmap=None):
+    """A device tensor ((H, W), (1, H, W) or (1, 1, H, W)): coloured on the device with the reference's
+    INFERNO map (or `cmap`, a name of nconv_amd.COLORMAPS) by visualize.colorize and written in R, G, B
+    order, which is the picture cv2.imwrite makes of the reference's BGR array. A host array with a cmap
+    name: the same rules in numpy. A host array without one: the grayscale image, as before."""
+    if torch.is_tensor(depth_data) and depth_data.is_cuda:
+        img = _m.visualize.colorize(depth_data.detach().float(), cmap="inferno" if cmap is None else cmap)
+        if img.shape[0] != 1:
+            raise ValueError(f"save_depth: one image per file, got a batch of {img.shape[0]}")
+        return _m.visualize.write_png8(path, img[0])
+    if cmap is not None:
+        a = depth_data.detach().numpy() if torch.is_tensor(depth_data) else np.asarray(depth_data)
+        a = a.reshape(a.shape[-2:]) if a.ndim > 2 and a.size == a.shape[-2] * a.shape[-1] else a
+        return _m.visualize.write_png8(path, _m.visualize.colorize_host(a, cmap))
     d = np.asarray(depth_data, dtype=np.float64)
     lo, hi = float(d.min()), float(d.max())
     img = np.zeros(d.shape, np.uint8) if hi <= lo else ((d - lo) / (hi - lo) * 255.0 + 0.5).astype(np.uint8)

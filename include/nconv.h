@@ -729,6 +729,61 @@ size_t nconv_lidar_project_workspace_bytes(int B, int H, int W, int with_index);
 int nconv_lidar_project(const struct nconv_lidar_project* d, float* depth, int* index, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Added under ABI 27 (purely additive: two new entry points and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). A depth plane -> the picture of it: uint8 (B, H, W, 3)
+ * through a 256-entry colour table. Replaces the reference's save_depth arithmetic (utils.py:12-16:
+ * min-max normalise on the host, cv2.applyColorMap(..., COLORMAP_INFERNO)); the builtin tables are the
+ * 256 listed colours of matplotlib's maps times 255, rounded (tools/gen_colormaps.py), which is how
+ * OpenCV's tables of the same names are defined. Parity with cv2 itself is not pinned by a test.
+ * Per pixel value v of image b, every operation one fp32 rounding (no FMA):
+ *   empty   iff v is not finite or v <= floor (floor = -inf: only the non-finite values)
+ *   lo, hi  auto_range: the minimum and maximum of image b's non-empty source pixels; else vmin, vmax
+ *   s       = 255.0f / (hi - lo)                                     (IEEE division)
+ *   idx     = clamp((int)rintf((v - lo) * s), 0, 255)                (ties to even)
+ *             the clamp is made on the float: a product beyond the int range saturates, NaN gives 0;
+ *             hi <= lo: idx = 0 for every non-empty pixel
+ * radius r > 0 (a sparse plane drawn as squares): an output pixel shows the smallest non-empty value of
+ * its (2r + 1) x (2r + 1) window clipped at the image border, and is empty if the window holds none.
+ * lo and hi always come from the source plane, not from the windows.
+ * Output: out[b][i][j][0..2] = table[idx] (R, G, B; B, G, R with bgr) for a non-empty pixel; for an
+ * empty one the background pixel's three bytes as they are (bgr does not reorder them), or, without a
+ * background, empty_rgb (R, G, B; written B, G, R with bgr). The result is a function of the input
+ * alone: identical on every run.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_colorize`
+ * or nconv_depth_colorize_desc) */
+typedef struct nconv_depth_colorize {
+    int B, H, W;
+    int radius;                         /* 0 .. 4                                                    */
+    const float* depth;                 /* fp32 view: B planes of H rows of W, 4-byte aligned        */
+    long long image_stride;             /* elements; ignored when B == 1                             */
+    long long row_stride;               /* elements, >= W (a cropped DNET output works)              */
+    const unsigned char* lut;           /* 256 x 3 uint8 R, G, B on the device, or NULL: cmap_id     */
+    int cmap_id;                        /* 0 inferno, 1 magma, 2 viridis, 3 turbo, 4 gray            */
+    int auto_range;                     /* nonzero: per-image min / max (needs the workspace)        */
+    float vmin, vmax;                   /* lo, hi when auto_range == 0                               */
+    float floor;                        /* empty: v <= floor; -INFINITY: none but non-finite values  */
+    int bgr;                            /* nonzero: write B, G, R                                    */
+    const unsigned char* background;    /* optional interleaved uint8 (B, H, W, 3) view              */
+    long long background_image_stride;  /* bytes; ignored when B == 1                                */
+    long long background_row_stride;    /* bytes, >= 3 * W                                           */
+    unsigned char empty_rgb[3];         /* an empty pixel without a background                       */
+} nconv_depth_colorize_desc;
+
+/* 8 * B bytes: a minimum and a maximum key per image. 0 for B <= 0. */
+size_t nconv_depth_colorize_workspace_bytes(int B);
+
+/* out: (B, H, W, 3) contiguous uint8, any alignment, overwritten entirely. With auto_range three
+ * kernels on `stream` (range reset, range reduce, map) and workspace must hold
+ * nconv_depth_colorize_workspace_bytes(B) bytes, 8-byte aligned (overwritten); with a fixed range one
+ * kernel, and the workspace is not used. No host synchronisation, no allocation, no waiting between
+ * workgroups. -EINVAL before any launch for a NULL descriptor / depth / out, B, H or W <= 0,
+ * B * H * W >= 2^31, radius outside 0..4, cmap_id outside 0..4 beside a NULL lut, NaN vmin or vmax
+ * without auto_range, NaN floor, a workspace that is NULL, short or misaligned with auto_range, depth
+ * not 4-byte aligned, and a depth or background view whose strides are smaller than its rows / images
+ * or whose image spans 2^31 bytes or more. */
+int nconv_depth_colorize(const struct nconv_depth_colorize* d, unsigned char* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,8 +16,11 @@ from .frames import Ingest, export_depth16, ingest, write_depth_png16
 from .pointcloud import PointCloud, backproject, backproject_map, write_ply
 from . import lidar
 from .lidar import LidarProjector, kitti_projection, project_points, projection_from_k, read_velodyne_bin
+from . import visualize
+from .visualize import COLORMAPS, Colorizer, colorize, overlay, write_png8
 
-__all__ = ["LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",
+__all__ = ["COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
+"LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",
 "PointCloud", "backproject", "backproject_map", "write_ply","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
            "SETP1_NCONV", "crop_hw", "SETP2_BP_EXPORT", "SETP2_BP_TRAIN", "RGBEncoder", "DepthMetrics",
            "depth_metric_sums", "Ingest", "export_depth16", "ingest", "write_depth_png16"]

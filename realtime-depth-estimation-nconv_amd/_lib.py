@@ -35,6 +35,8 @@ DENSE_MATHS = {"fp32": 0, "bf16x9": 2, "bf16x6": 3}
 FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
 # enum nconv_color_kind
 COLOR_NONE, COLOR_F32_PLANAR, COLOR_U8_INTERLEAVED = 0, 1, 2
+# nconv_depth_colorize.cmap_id
+CMAP_IDS = {"inferno": 0, "magma": 1, "viridis": 2, "turbo": 3, "gray": 4}
 
 EXPORTED = (
     "nconv_abi_version",
@@ -82,6 +84,8 @@ EXPORTED = (
     "nconv_backproject_points",
     "nconv_lidar_project_workspace_bytes",
     "nconv_lidar_project",
+    "nconv_depth_colorize_workspace_bytes",
+    "nconv_depth_colorize",
 )
 
 
@@ -167,6 +171,15 @@ class NconvLidarProject(ctypes.Structure):
                 ("points", ctypes.c_void_p), ("n_rows", ctypes.c_longlong), ("offsets", ctypes.c_void_p),
                 ("m", ctypes.c_void_p), ("m_image_stride", ctypes.c_longlong), ("z_min", ctypes.c_float),
                 ("z_max", ctypes.c_float)]
+
+
+class NconvDepthColorize(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("radius", ctypes.c_int),
+                ("depth", ctypes.c_void_p), ("image_stride", ctypes.c_longlong), ("row_stride", ctypes.c_longlong),
+                ("lut", ctypes.c_void_p), ("cmap_id", ctypes.c_int), ("auto_range", ctypes.c_int),
+                ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("floor", ctypes.c_float), ("bgr", ctypes.c_int),
+                ("background", ctypes.c_void_p), ("background_image_stride", ctypes.c_longlong),
+                ("background_row_stride", ctypes.c_longlong), ("empty_rgb", ctypes.c_ubyte * 3)]
 
 
 _lib = None
@@ -273,6 +286,10 @@ def _declare(lib):
     lib.nconv_lidar_project_workspace_bytes.argtypes = [I, I, I, I]
     lib.nconv_lidar_project.restype = I
     lib.nconv_lidar_project.argtypes = [ctypes.POINTER(NconvLidarProject), P, P, P, ctypes.c_size_t, P]
+    lib.nconv_depth_colorize_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_depth_colorize_workspace_bytes.argtypes = [I]
+    lib.nconv_depth_colorize.restype = I
+    lib.nconv_depth_colorize.argtypes = [ctypes.POINTER(NconvDepthColorize), P, P, ctypes.c_size_t, P]
 
 
 def lib():

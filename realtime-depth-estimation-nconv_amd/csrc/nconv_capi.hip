@@ -891,4 +891,46 @@ int nconv_lidar_project(const struct nconv_lidar_project* d, float* depth, int* 
     return rc ? fail(rc, fn, why) : 0;
 }
 
+size_t nconv_depth_colorize_workspace_bytes(int B) { return B > 0 ? (size_t)8 * B : 0; }
+
+int nconv_depth_colorize(const struct nconv_depth_colorize* d, unsigned char* out, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_depth_colorize";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->depth || !out) return fail(-22, fn, "null depth or out");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)d->B * d->H * d->W >= (1LL << 31))
+        return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->radius < 0 || d->radius > 4) return fail(-22, fn, "radius must be in [0, 4]");
+    if (!d->lut && (d->cmap_id < 0 || d->cmap_id > 4))
+        return fail(-22, fn, "cmap_id must be in [0, 4] (or give a lut)");
+    if (!d->auto_range && (d->vmin != d->vmin || d->vmax != d->vmax)) return fail(-22, fn, "vmin or vmax is NaN");
+    if (d->floor != d->floor) return fail(-22, fn, "floor is NaN");
+    if (d->auto_range) {
+        if (!workspace || workspace_bytes < nconv_depth_colorize_workspace_bytes(d->B))
+            return fail(-22, fn, "workspace too small");
+        if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    }
+    if ((size_t)d->depth % 4) return fail(-22, fn, "depth not 4-byte aligned");
+    nconv::ColorizeArgs a{};
+    a.B = d->B, a.H = d->H, a.W = d->W;
+    if (const char* why = view_args(d->depth, a.B, a.H, a.W, 4, d->image_stride, d->row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.d))
+        return fail(-22, fn, why);
+    if (d->background) {
+        if (const char* why = view_args(d->background, a.B, a.H, 3LL * a.W, 1, d->background_image_stride,
+                                        d->background_row_stride, kNoStrideLimit, 4, kViewBytes, a.bg))
+            return fail(-22, fn, (std::string("background: ") + why).c_str());
+    }
+    a.lut = d->lut, a.cmap = d->cmap_id, a.auto_range = d->auto_range != 0;
+    a.radius = d->radius, a.bgr = d->bgr != 0;
+    a.lo = d->vmin, a.hi = d->vmax, a.floor = d->floor;
+    const unsigned e0 = d->empty_rgb[a.bgr ? 2 : 0], e1 = d->empty_rgb[1], e2 = d->empty_rgb[a.bgr ? 0 : 2];
+    a.empty = e0 | (e1 << 8) | (e2 << 16);
+    a.out = out, a.range = a.auto_range ? (unsigned*)workspace : nullptr;
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_colorize(a, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

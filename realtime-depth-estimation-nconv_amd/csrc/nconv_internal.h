@@ -307,4 +307,20 @@ struct LidarArgs {
 int launch_lidar_project(const LidarArgs& a, float* depth, int* index, unsigned long long* keys, hipStream_t st,
                          const char** why);
 
+// Depth plane -> colour image (nconv_depth_colorize), colorize.hip.
+struct ColorizeArgs {
+    PlaneView d;               // fp32, strides in elements
+    PlaneView bg;              // base null: none; uint8 interleaved, strides in bytes; wide: 4-byte aligned
+    int B, H, W;
+    const unsigned char* lut;  // 256 x 3 RGB on the device, or null: the builtin table cmap
+    int cmap;
+    int auto_range;            // lo / hi from range[2 b], range[2 b + 1] (order-preserving keys)
+    int radius, bgr;
+    float lo, hi, floor;
+    unsigned empty;            // the colour of an empty pixel, packed as the table entries are
+    unsigned char* out;        // (B, H, W, 3) contiguous
+    unsigned* range;           // 2 * B keys (auto_range)
+};
+int launch_depth_colorize(const ColorizeArgs& a, hipStream_t st, const char** why);
+
 }  // namespace nconv

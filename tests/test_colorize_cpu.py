@@ -1,0 +1,380 @@
+"""CPU: the numpy reference of the depth colouring against hand-written cases (ties, clamps, a constant
+plane, an all-empty plane, the window minimum); the committed colour tables against a fresh generation
+and known entries; the two entry points are exported, declared and bound with the C struct's layout;
+every malformed call fails on the host with -22 before any launch; visualize.* refuse malformed
+arguments and CPU tensors; compat save_depth on a host array writes what it always wrote."""
+import ctypes
+import importlib.util
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import colorize_cases as CC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "nconv.h")
+NEW = ("nconv_depth_colorize_workspace_bytes", "nconv_depth_colorize")
+GRAY = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+
+
+# ---- the reference ---------------------------------------------------------------------------------
+def test_reference_ties_and_clamps():
+    """vmin = 0, vmax = 255: s == 1, so idx = clamp(rint(v)). k + 0.5 goes to the even neighbour."""
+    v = np.array([[[0.5, 1.5, 2.5, 3.5, 254.5, 253.5, 0.0, 255.0, 127.49, 127.51, -4.0, 300.0, 1e30, -1e30,
+                    np.nan, np.inf, -np.inf]]], dtype=np.float32)
+    got = CC.colorize_ref(v, GRAY, vmin=0.0, vmax=255.0, empty=(9, 8, 7))
+    want = [0, 2, 2, 4, 254, 254, 0, 255, 127, 128, 0, 255, 255, 0]
+    assert got[0, 0, :14, 0].tolist() == want and (got[0, 0, :14, 1] == got[0, 0, :14, 0]).all()
+    assert got[0, 0, 14:].tolist() == [[9, 8, 7]] * 3
+    # a floor makes the values at and below it empty; bgr reverses the table's and empty's channels only
+    table = np.stack([np.arange(256), np.full(256, 1), np.full(256, 2)], axis=1).astype(np.uint8)
+    bg = np.full((1, 1, 17, 3), 200, dtype=np.uint8)
+    bg[..., 0] = 100
+    got = CC.colorize_ref(v, table, vmin=0.0, vmax=255.0, floor=0.5, order="bgr", background=bg)
+    assert got[0, 0, 0].tolist() == [100, 200, 200] and got[0, 0, 6].tolist() == [100, 200, 200]  # 0.5, 0.0
+    assert got[0, 0, 1].tolist() == [2, 1, 2] and got[0, 0, 10].tolist() == [100, 200, 200]       # 1.5, -4
+    got = CC.colorize_ref(v, table, vmin=0.0, vmax=255.0, order="bgr", empty=(9, 8, 7))
+    assert got[0, 0, 14].tolist() == [7, 8, 9]
+
+
+def test_reference_auto_range_constant_and_empty():
+    v = np.array([[[2.0, 4.0, 3.0, np.nan]], [[5.0, 5.0, 5.0, 5.0]], [[np.nan, np.inf, -np.inf, np.nan]]],
+                 dtype=np.float32)
+    got = CC.colorize_ref(v, GRAY, empty=(1, 2, 3))
+    assert got[0, 0, :, 0].tolist() == [0, 255, 128, 1] and got[0, 0, 3].tolist() == [1, 2, 3]  # 127.5 -> 128
+    assert (got[1] == 0).all()                       # hi == lo: index 0
+    assert (got[2] == np.array([1, 2, 3])).all()     # no non-empty pixel
+    # the per-image ranges do not leak: image 0 alone gives the same picture
+    assert np.array_equal(CC.colorize_ref(v[:1], GRAY, empty=(1, 2, 3)), got[:1])
+    # floor = 0: zeros and negatives are empty, the range comes from the rest
+    v = np.array([[[0.0, -1.0, 10.0, 20.0, -0.0]]], dtype=np.float32)
+    got = CC.colorize_ref(v, GRAY, floor=0.0, empty=(7, 7, 7))
+    assert got[0, 0, :, 0].tolist() == [7, 7, 0, 255, 7]
+    got = CC.colorize_ref(v, GRAY, empty=(7, 7, 7))
+    assert got[0, 0, :, 0].tolist() == [12, 0, 134, 255, 12]  # (0 + 1) * (255 / 21) = 12.14, 11 * 12.14 = 133.6
+
+
+def test_reference_window_minimum():
+    v = np.zeros((1, 5, 6), dtype=np.float32)
+    v[0, 0, 0], v[0, 2, 3], v[0, 2, 4] = 10.0, 30.0, 20.0
+    got = CC.colorize_ref(v, GRAY, floor=0.0, radius=1, empty=(1, 1, 1))[0, :, :, 0]
+    # range 10 .. 30 from the source plane: 10 -> 0, 20 -> 128 (127.5, to even), 30 -> 255
+    want = np.ones((5, 6), dtype=np.uint8)
+    want[0:2, 0:2] = 0
+    want[1:4, 2:5] = 255
+    want[1:4, 3:6] = 128  # the nearer return on top
+    assert np.array_equal(got, want)
+    # a window larger than the image: every pixel shows the image's minimum
+    got = CC.colorize_ref(v, GRAY, floor=0.0, radius=4, vmin=0.0, vmax=255.0)[0, :, :, 0]
+    assert (got[:, :5] == 10).all() and (got[:, 5] == 20).all()
+    assert np.array_equal(CC.colorize_ref(v, GRAY, radius=0), CC.colorize_ref(v, GRAY))
+
+
+# ---- the tables --------------------------------------------------------------------------------------
+def test_tables_known_entries(nconv_amd):
+    C = nconv_amd.COLORMAPS
+    assert sorted(C) == ["gray", "inferno", "magma", "turbo", "viridis"] and C is nconv_amd.visualize.COLORMAPS
+    for t in C.values():
+        assert t.dtype == np.uint8 and t.shape == (256, 3)
+    assert [tuple(C["inferno"][i]) for i in (0, 128, 255)] == [(0, 0, 4), (188, 55, 84), (252, 255, 164)]
+    assert np.array_equal(C["gray"], GRAY)
+    assert nconv_amd._lib.CMAP_IDS == {"inferno": 0, "magma": 1, "viridis": 2, "turbo": 3, "gray": 4}
+
+
+def _generator():
+    spec = importlib.util.spec_from_file_location("gen_colormaps", os.path.join(ROOT, "tools", "gen_colormaps.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_tables_equal_a_fresh_generation(nconv_amd):
+    pytest.importorskip("matplotlib")
+    gen = _generator()
+    t = gen.tables()
+    assert tuple(t) == gen.NAMES == ("inferno", "magma", "viridis", "turbo")
+    for name in gen.NAMES:
+        assert np.array_equal(t[name], nconv_amd.COLORMAPS[name]), name
+    assert open(gen.HEADER).read() == gen.header_text(t)
+    assert open(gen.MODULE).read() == gen.module_text(t)
+
+
+def test_header_table_holds_the_python_bytes(nconv_amd):
+    """Without matplotlib too: the numbers of csrc/colormaps.h are the bytes of the Python literal."""
+    src = open(os.path.join(ROOT, "realtime-depth-estimation-nconv_amd", "csrc", "colormaps.h")).read()
+    blocks = re.findall(r"\{\s*// (\w+)\n(.*?)\}", src, re.S)
+    assert [b[0] for b in blocks] == ["inferno", "magma", "viridis", "turbo"]
+    for name, body in blocks:
+        vals = np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint8)
+        assert np.array_equal(vals.reshape(256, 3), nconv_amd.COLORMAPS[name]), name
+
+
+# ---- ABI -------------------------------------------------------------------------------------------
+def test_entry_points_exported_and_declared(nconv_amd):
+    src = open(HEADER).read()
+    declared = set(re.findall(r"^\s*(?:const\s+)?\w+\*?\s+\**(nconv_\w+)\s*\(", src, re.M))
+    lib = nconv_amd._lib.lib()
+    for name in NEW:
+        assert name in declared and name in nconv_amd._lib.EXPORTED
+        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+    v = int(re.search(r"#define NCONV_ABI_VERSION (\d+)", src).group(1))
+    assert lib.nconv_abi_version() == v == nconv_amd._lib.ABI_VERSION
+
+
+@pytest.fixture(scope="module")
+def host_report(nconv_amd, tmp_path_factory):
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("gcc not available")
+    lib = nconv_amd._lib.LIB_PATH
+    exe = str(tmp_path_factory.mktemp("host") / "colorize_host")
+    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "host", "colorize_host.c"), "-o", exe, lib,
+                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
+    return json.loads(r.stdout)
+
+
+def test_struct_layout_matches_ctypes(nconv_amd, host_report):
+    S = nconv_amd._lib.NconvDepthColorize
+    want = {"nconv_depth_colorize": [0, ctypes.sizeof(S)]}
+    for f, _ in S._fields_:
+        d = getattr(S, f)
+        want[f"nconv_depth_colorize.{f}"] = [d.offset, d.size]
+    c = {k: v for k, v in host_report.items() if k.startswith("nconv_depth_colorize")}
+    assert len(c) == 19 and c == want
+    assert host_report["desc_typedef"] == ctypes.sizeof(S)
+
+
+HOST_REJECTS = {
+    "null_descriptor": "null descriptor", "null_depth": "null depth or out", "null_out": "null depth or out",
+    "B_zero": "non-positive", "H_zero": "non-positive", "W_negative": "non-positive",
+    "too_many_pixels": "below 2^31", "radius_negative": "radius", "radius_5": "radius", "cmap_id_5": "cmap_id",
+    "cmap_id_negative": "cmap_id", "vmin_nan": "vmin or vmax is NaN", "vmax_nan": "vmin or vmax is NaN",
+    "floor_nan": "floor is NaN", "workspace_null": "workspace too small", "workspace_short": "workspace too small",
+    "workspace_misaligned": "8-byte aligned", "depth_misaligned": "4-byte aligned",
+    "row_stride_short": "row stride smaller than W", "image_stride_short": "image stride smaller",
+    "background_row_stride_short": "background: row stride smaller",
+}
+
+
+def test_host_calls(nconv_amd, host_report):
+    assert host_report["abi"][0] == host_report["abi"][1] == nconv_amd._lib.ABI_VERSION
+    got = {k[3:]: v for k, v in host_report.items() if k.startswith("rc_")}
+    assert set(got) == set(HOST_REJECTS)
+    for key, msg in HOST_REJECTS.items():
+        rc, err = got[key]
+        assert rc == -22 and err.startswith("nconv_depth_colorize: ") and msg in err, (key, rc, err)
+    assert host_report["workspace"] == [8, 64, 0, 0]
+
+
+# ---- host validation through ctypes ----------------------------------------------------------------
+FAKE = {n: 0x10000 * (q + 1) for q, n in enumerate(("depth", "out", "ws", "lut", "bg"))}
+NAN = float("nan")
+
+
+def _desc(L, **kw):
+    d = L.NconvDepthColorize()
+    d.B, d.H, d.W, d.radius = 2, 4, 8, 2
+    d.depth, d.image_stride, d.row_stride = FAKE["depth"], 32, 8
+    d.cmap_id, d.auto_range, d.floor = 3, 1, float("-inf")
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+@pytest.mark.parametrize("bad,msg", [
+    (dict(depth=None), "null depth or out"),
+    (dict(B=0), "non-positive"), (dict(H=-3), "non-positive"), (dict(W=0), "non-positive"),
+    (dict(B=1 << 15, H=1 << 8, W=1 << 8), "below 2^31"),
+    (dict(radius=-1), "radius"), (dict(radius=5), "radius"),
+    (dict(cmap_id=5), "cmap_id"), (dict(cmap_id=-1), "cmap_id"),
+    (dict(auto_range=0, vmin=NAN, vmax=1.0), "vmin or vmax is NaN"),
+    (dict(auto_range=0, vmin=0.0, vmax=NAN), "vmin or vmax is NaN"),
+    (dict(floor=NAN), "floor is NaN"),
+    (dict(depth=FAKE["depth"] + 2), "4-byte aligned"),
+    (dict(row_stride=7), "row stride smaller than W"), (dict(image_stride=31), "image stride smaller"),
+    (dict(row_stride=1 << 29, image_stride=1 << 40), "plane too large"),
+    (dict(background=FAKE["bg"], background_row_stride=23, background_image_stride=96), "background: row stride"),
+    (dict(background=FAKE["bg"], background_row_stride=24, background_image_stride=95), "background: image stride"),
+])
+def test_call_rejects_bad_descriptors(nconv_amd, bad, msg):
+    L = nconv_amd._lib
+    lib = L.lib()
+    d = _desc(L, **bad)
+    assert lib.nconv_depth_colorize(ctypes.byref(d), FAKE["out"] + 1, FAKE["ws"], 16, None) == -22
+    assert msg in lib.nconv_last_error().decode()
+
+
+def test_call_rejects_bad_arguments(nconv_amd):
+    L = nconv_amd._lib
+    lib = L.lib()
+    d = _desc(L)
+    assert lib.nconv_depth_colorize_workspace_bytes(2) == 16
+    assert lib.nconv_depth_colorize_workspace_bytes(0) == 0 and lib.nconv_depth_colorize_workspace_bytes(-1) == 0
+    call = lambda out=FAKE["out"], ws=FAKE["ws"], n=16: lib.nconv_depth_colorize(ctypes.byref(d), out, ws, n, None)
+    assert lib.nconv_depth_colorize(None, FAKE["out"], FAKE["ws"], 16, None) == -22
+    assert "null descriptor" in lib.nconv_last_error().decode()
+    for kw, msg in ((dict(out=None), "null depth or out"), (dict(ws=None), "workspace too small"),
+                    (dict(n=15), "workspace too small"), (dict(n=0), "workspace too small"),
+                    (dict(ws=FAKE["ws"] + 4), "8-byte aligned")):
+        assert call(**kw) == -22, msg
+        assert msg in lib.nconv_last_error().decode(), msg
+    # a lut makes cmap_id irrelevant: the next check (the workspace) is what refuses this call
+    d = _desc(L, lut=FAKE["lut"], cmap_id=77)
+    assert call(ws=None) == -22 and "workspace too small" in lib.nconv_last_error().decode()
+
+
+# ---- Python argument checks ------------------------------------------------------------------------
+def test_visualize_refuses_cpu_tensors_and_bad_arguments(nconv_amd):
+    V = nconv_amd.visualize
+    assert nconv_amd.colorize is V.colorize and nconv_amd.Colorizer is V.Colorizer
+    assert nconv_amd.overlay is V.overlay and nconv_amd.write_png8 is V.write_png8
+    d, bg = torch.ones(2, 1, 4, 8), torch.zeros(2, 4, 8, 3, dtype=torch.uint8)
+    for fn in (V.colorize, lambda x, **kw: V.Colorizer((4, 8), B=2, **kw)(x)):
+        with pytest.raises(RuntimeError, match="ROCm devices only"):
+            fn(d)
+        with pytest.raises(RuntimeError, match="ROCm devices only"):
+            fn(d, vmin=0.0, vmax=80.0, cmap="turbo", radius=2, order="bgr", empty=(1, 2, 3), floor=0.0)
+        with pytest.raises(ValueError, match="both vmin and vmax"):
+            fn(d, vmin=0.0)
+        with pytest.raises(ValueError, match="both vmin and vmax"):
+            fn(d, vmax=1.0)
+        with pytest.raises(ValueError, match="NaN"):
+            fn(d, vmin=0.0, vmax=NAN)
+        with pytest.raises(ValueError, match="floor is NaN"):
+            fn(d, floor=NAN)
+        for r in (-1, 5, 1.0, True):
+            with pytest.raises(ValueError, match="radius"):
+                fn(d, radius=r)
+        with pytest.raises(ValueError, match="unknown cmap"):
+            fn(d, cmap="jet")
+        with pytest.raises(ValueError, match="empty"):
+            fn(d, empty=(0, 0, 256))
+        with pytest.raises(ValueError, match="empty"):
+            fn(d, empty=(0, 0))
+        with pytest.raises(TypeError, match="empty"):
+            fn(d, empty=3)
+        with pytest.raises(ValueError, match="order"):
+            fn(d, order="rbg")
+    with pytest.raises(RuntimeError, match="ROCm devices only"):
+        V.colorize(d, background=bg)
+    with pytest.raises(RuntimeError, match="ROCm devices only"):
+        V.overlay(d, bg)
+    with pytest.raises(RuntimeError, match="ROCm devices only"):
+        V.colorize(d, cmap=torch.zeros(256, 3, dtype=torch.uint8))
+    with pytest.raises(TypeError, match="depth"):
+        V.colorize(d.double())
+    with pytest.raises(TypeError, match="depth must be a tensor"):
+        V.colorize(np.ones((4, 8), dtype=np.float32))
+    with pytest.raises(ValueError, match="depth of shape"):
+        V.colorize(torch.ones(2, 3, 4, 8))
+    with pytest.raises(ValueError, match="depth of shape"):
+        V.colorize(torch.ones(4, 16)[:, ::2])
+    with pytest.raises(TypeError, match="cmap"):
+        V.colorize(d, cmap=torch.zeros(256, 3))
+    with pytest.raises(ValueError, match="cmap tensor"):
+        V.colorize(d, cmap=torch.zeros(3, 256, dtype=torch.uint8))
+    with pytest.raises(ValueError, match="cmap tensor"):
+        V.colorize(d, cmap=torch.zeros(256, 6, dtype=torch.uint8)[:, ::2])
+    with pytest.raises(TypeError, match="background"):
+        V.colorize(d, background=bg.float())
+    with pytest.raises(ValueError, match="background"):
+        V.colorize(d, background=bg[:1])
+    with pytest.raises(ValueError, match="not interleaved"):
+        V.colorize(d, background=torch.zeros(2, 3, 4, 8, dtype=torch.uint8).permute(0, 2, 3, 1))
+    with pytest.raises(TypeError, match="size"):
+        V.Colorizer(8)
+    with pytest.raises(ValueError, match="positive"):
+        V.Colorizer((0, 8))
+    with pytest.raises(ValueError, match="positive"):
+        V.Colorizer((4, 8), B=0)
+    with pytest.raises(TypeError, match="not \\['out'\\]"):
+        V.Colorizer((4, 8), out=None)
+    with pytest.raises(ValueError, match="empty"):
+        V.workspace_bytes(0)
+    assert V.workspace_bytes(3) == 24
+
+
+def test_write_png8_round_trip(nconv_amd, tmp_path):
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    rgb = rng.integers(0, 256, (5, 7, 3)).astype(np.uint8)
+    p = str(tmp_path / "a.png")
+    for img in (rgb, torch.from_numpy(rgb), rgb[None], torch.from_numpy(rgb)[None, None]):
+        nconv_amd.write_png8(p, img)
+        back = Image.open(p)
+        assert back.mode == "RGB" and np.array_equal(np.asarray(back), rgb)
+    for img in (rgb[..., 0], rgb[None, ..., 0], np.ascontiguousarray(rgb[:1, :3, 0])):
+        nconv_amd.write_png8(p, img)
+        back = Image.open(p)
+        assert back.mode == "L" and np.array_equal(np.asarray(back), img.reshape(img.shape[-2:]))
+    with pytest.raises(TypeError, match="uint8"):
+        nconv_amd.write_png8(p, rgb.astype(np.uint16))
+    with pytest.raises(ValueError, match="one"):
+        nconv_amd.write_png8(p, np.zeros((2, 5, 7, 3), dtype=np.uint8))
+    with pytest.raises(ValueError, match="one"):
+        nconv_amd.write_png8(p, np.zeros(5, dtype=np.uint8))
+
+
+# ---- compat save_depth -----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def compat_utils(nconv_amd):
+    """compat/utils.py under a private module name, with compat/ importable while it loads (its
+    `from dataset.kittiloader import *`); sys.path and sys.modules are put back afterwards."""
+    path = os.path.join(ROOT, "compat")
+    sys.path.insert(0, path)
+    saved = {k: sys.modules.get(k) for k in ("dataset", "dataset.kittiloader")}
+    try:
+        for k in saved:
+            sys.modules.pop(k, None)
+        spec = importlib.util.spec_from_file_location("compat_utils_under_test", os.path.join(path, "utils.py"))
+        utils = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(utils)
+        yield utils
+    finally:
+        sys.path.remove(path)
+        for k, v in saved.items():
+            sys.modules.pop(k, None)
+            if v is not None:
+                sys.modules[k] = v
+
+
+def _save_depth_as_it_was(depth_data, path):
+    d = np.asarray(depth_data, dtype=np.float64)
+    lo, hi = float(d.min()), float(d.max())
+    img = np.zeros(d.shape, np.uint8) if hi <= lo else ((d - lo) / (hi - lo) * 255.0 + 0.5).astype(np.uint8)
+    from PIL import Image
+    Image.fromarray(img).save(path)
+
+
+@pytest.mark.parametrize("kind", ["random", "constant"])
+def test_save_depth_host_array_unchanged(compat_utils, tmp_path, kind):
+    rng = np.random.default_rng(3)
+    d = rng.uniform(0.0, 80.0, (9, 13)).astype(np.float32) if kind == "random" else np.full((9, 13), 4.0, np.float32)
+    a, b = str(tmp_path / "new.png"), str(tmp_path / "old.png")
+    for data in (d, torch.from_numpy(d)):
+        compat_utils.save_depth(data, a)
+        _save_depth_as_it_was(data, b)
+        assert open(a, "rb").read() == open(b, "rb").read()
+
+
+def test_save_depth_host_array_with_cmap(nconv_amd, compat_utils, tmp_path):
+    from PIL import Image
+    rng = np.random.default_rng(4)
+    d = CC.plane(rng, 1, 9, 13, fill=1.0)[0]
+    p = str(tmp_path / "c.png")
+    for name in ("inferno", "turbo", "gray"):
+        want = CC.colorize_ref(d[None], nconv_amd.COLORMAPS[name])[0]
+        for data in (d, torch.from_numpy(d), d[None, None]):
+            compat_utils.save_depth(data, p, cmap=name)
+            assert np.array_equal(np.asarray(Image.open(p)), want), name
+    with pytest.raises(ValueError, match="unknown cmap"):
+        compat_utils.save_depth(d, p, cmap="jet")
