@@ -784,6 +784,61 @@ size_t nconv_depth_colorize_workspace_bytes(int B);
 int nconv_depth_colorize(const struct nconv_depth_colorize* d, unsigned char* out, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Added under ABI 27 (purely additive: two new entry points and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). Surface normals of a depth map on the image grid, from the
+ * same descriptor nconv_backproject_map takes (checked in the same way; color is ignored): what
+ * point-to-plane ICP, meshing, ground segmentation and shaded rendering expect beside the points. With
+ * PyTorch ops the same result is about fifteen elementwise passes over (B, 3, H, W).
+ * Every arithmetic operation below is one fp32 rounding in the stated order, no FMA contraction;
+ * division and square root are IEEE (correctly rounded). For image b, pixel (i, j):
+ *   V(i, j)   the pixel is inside the image and valid by nconv_backproject's rule
+ *             (z > z_min && z <= z_max && (conf == NULL || conf >= conf_min)); a pixel outside the
+ *             image is not valid whatever z_min is
+ *   P(i, j)   nconv_backproject's point (x, y, z), bit for bit
+ * A centre c with V false has no normal. Otherwise, with z its depth,
+ *   tol       = jump_abs + jump_rel * z                       (one multiply, one add)
+ *   usable(n) = V(n) && (gate off || fabsf(z_n - z) <= tol)   (comparisons: a NaN is not usable)
+ *               the gate is off when jump_rel == 0 && jump_abs == 0
+ *   tu        from R = (i, j + 1) and L = (i, j - 1): both usable P(R) - P(L); only R: P(R) - P(c);
+ *             only L: P(c) - P(L); neither: no normal
+ *   tv        from D = (i + 1, j) and T = (i - 1, j) by the same rule, D in the role of R
+ *   c = tv x tu:  cx = tv.y * tu.z - tv.z * tu.y,  cy = tv.z * tu.x - tv.x * tu.z,
+ *                 cz = tv.x * tu.y - tv.y * tu.x      (a fronto-parallel surface gives (0, 0, -1))
+ *   d         = (cx * P.x + cy * P.y) + cz * P.z; d > 0: c = -c, so that n . P <= 0 (towards the camera)
+ *   l         = sqrtf((cx * cx + cy * cy) + cz * cz); the pixel has a normal iff l > 0 && l < INFINITY
+ *   n         = (cx / l, cy / l, cz / l)
+ * H == 1 or W == 1 is legal and yields no normal anywhere. The result is a function of the input
+ * alone: identical on every run. */
+typedef struct nconv_normals_opts {
+    float jump_rel, jump_abs;      /* both 0: no discontinuity gate */
+    unsigned char empty_rgb[3];    /* picture: a pixel without a normal */
+} nconv_normals_opts;              /* NULL: all zero */
+
+/* Either or both of (NULL: skip)
+ *   normals  (B, 3, H, W) contiguous fp32, planes nx, ny, nz; NaN in all three where the pixel has no
+ *            normal. 4-byte aligned.
+ *   image    (B, H, W, 3) contiguous uint8, any alignment: the camera-space normal picture,
+ *            R = q(nx), G = q(-ny), B = q(-nz) with q(t) = clamp(rintf((t * 0.5f + 0.5f) * 255.0f), 0, 255)
+ *            and (0.5f - t * 0.5f) for the negated channels; empty_rgb where there is no normal.
+ * One kernel on `stream`, no workspace, no host synchronisation; the picture is made without the fp32
+ * map reaching memory. No byte outside a view's extent is read. -EINVAL before any launch for whatever
+ * nconv_backproject_map refuses in d, both outputs NULL, a NaN or negative jump_rel or jump_abs, and
+ * normals not 4-byte aligned. */
+int nconv_depth_normals(const nconv_backproject* d, const nconv_normals_opts* o, float* normals,
+                        unsigned char* image, void* stream);
+
+/* The same normals for the rows of a packed cloud (index and offsets as nconv_backproject_points wrote
+ * them for the same d): normals[r] = three fp32, interleaved, the normal of pixel index[r] =
+ * (b * H + i) * W + j for every r < min(offsets[B], capacity), and (0, 0, 0) where that pixel has no
+ * normal (the PLY convention) or index[r] lies outside [0, B * H * W), for which nothing is read. Rows
+ * from min(offsets[B], capacity) on are not written. offsets[B] is read on the device; capacity is a
+ * host value and sizes the grid. One kernel, no workspace, no host synchronisation. capacity == 0 is
+ * legal and launches nothing. -EINVAL before any launch for whatever nconv_backproject_map refuses in
+ * d, a NaN or negative jump_rel or jump_abs, a negative capacity, a NULL index, offsets or normals
+ * beside capacity > 0, and index, offsets or normals not 4-byte aligned. */
+int nconv_depth_normals_points(const nconv_backproject* d, const nconv_normals_opts* o, const int* index,
+                               const int* offsets, long long capacity, float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

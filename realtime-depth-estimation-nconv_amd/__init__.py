@@ -13,7 +13,8 @@ from .dnet import DNET, SETP1_NCONV, crop_hw
 from .guided import SETP2_BP_EXPORT, SETP2_BP_TRAIN, RGBEncoder
 from .metrics import DepthMetrics, depth_metric_sums
 from .frames import Ingest, export_depth16, ingest, write_depth_png16
-from .pointcloud import PointCloud, backproject, backproject_map, write_ply
+from .pointcloud import (PointCloud, backproject, backproject_map, normal_image, normals, normals_and_image,
+                         write_ply)
 from . import lidar
 from .lidar import LidarProjector, kitti_projection, project_points, projection_from_k, read_velodyne_bin
 from . import visualize
@@ -21,6 +22,6 @@ from .visualize import COLORMAPS, Colorizer, colorize, overlay, write_png8
 
 __all__ = ["COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
 "LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",
-"PointCloud", "backproject", "backproject_map", "write_ply","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
+"PointCloud", "backproject", "backproject_map", "write_ply", "normals", "normal_image", "normals_and_image","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
            "SETP1_NCONV", "crop_hw", "SETP2_BP_EXPORT", "SETP2_BP_TRAIN", "RGBEncoder", "DepthMetrics",
            "depth_metric_sums", "Ingest", "export_depth16", "ingest", "write_depth_png16"]

@@ -86,6 +86,8 @@ EXPORTED = (
     "nconv_lidar_project",
     "nconv_depth_colorize_workspace_bytes",
     "nconv_depth_colorize",
+    "nconv_depth_normals",
+    "nconv_depth_normals_points",
 )
 
 
@@ -180,6 +182,10 @@ class NconvDepthColorize(ctypes.Structure):
                 ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("floor", ctypes.c_float), ("bgr", ctypes.c_int),
                 ("background", ctypes.c_void_p), ("background_image_stride", ctypes.c_longlong),
                 ("background_row_stride", ctypes.c_longlong), ("empty_rgb", ctypes.c_ubyte * 3)]
+
+
+class NconvNormalsOpts(ctypes.Structure):
+    _fields_ = [("jump_rel", ctypes.c_float), ("jump_abs", ctypes.c_float), ("empty_rgb", ctypes.c_ubyte * 3)]
 
 
 _lib = None
@@ -290,6 +296,11 @@ def _declare(lib):
     lib.nconv_depth_colorize_workspace_bytes.argtypes = [I]
     lib.nconv_depth_colorize.restype = I
     lib.nconv_depth_colorize.argtypes = [ctypes.POINTER(NconvDepthColorize), P, P, ctypes.c_size_t, P]
+    lib.nconv_depth_normals.restype = I
+    lib.nconv_depth_normals.argtypes = [ctypes.POINTER(NconvBackproject), ctypes.POINTER(NconvNormalsOpts), P, P, P]
+    lib.nconv_depth_normals_points.restype = I
+    lib.nconv_depth_normals_points.argtypes = [ctypes.POINTER(NconvBackproject), ctypes.POINTER(NconvNormalsOpts),
+                                               P, P, L, P, P]
 
 
 def lib():

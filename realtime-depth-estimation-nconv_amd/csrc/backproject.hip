@@ -13,7 +13,8 @@
 // cy = K[0][0], K[1][1], K[0][2], K[1][2] of image b's 3 x 3 matrix, read here (the other entries
 // are not read).
 //
-// A wave of 64 lanes takes four consecutive pixels per lane: one wave owns a segment of 256
+// The tiling, the validity rule and the point are defined in backproject_common.h, which normals.hip
+// shares. A wave of 64 lanes takes four consecutive pixels per lane: one wave owns a segment of 256
 // consecutive pixels of one image row, a block of four waves four segments. Depth, confidence and
 // colour are views read with plane_io.h's loaders (load4_f32, load4_rgb8); a lane with nothing to
 // read passes n = 0 and gets 0. No load touches memory outside the views.
@@ -26,77 +27,14 @@
 // storing only ranks below the capacity. Order comes from the scan alone: no atomics, no flag or
 // counter one workgroup waits on, so the result is the same on every run. No allocation and no host
 // synchronisation: the calls can be captured in a hipGraph.
-#include "nconv_internal.h"
+#include "backproject_common.h"
 
 namespace nconv {
 
 namespace {
 
-constexpr int kBT = 256;                // threads: four waves, one segment each
-constexpr int kSeg = 64 * 4;            // pixels per segment (four per lane)
 constexpr int kScanT = 1024;            // the scan's single workgroup
 constexpr int kScanE = 4;               // segments per thread and round
-
-struct Camera {
-    float fx, fy, cx, cy;
-};
-
-// where a wave works: image b, row i, first pixel j of the lane, n = its pixels inside the row (<= 0: none)
-struct Where {
-    int s, b, i, j, n;
-};
-
-__device__ __forceinline__ bool segment_of_wave(const BackprojectArgs& a, Where& w) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    w.s = (int)blockIdx.x * (kBT / 64) + wave;
-    if (w.s >= a.nseg) return false;
-    const int nsw = (a.W + kSeg - 1) / kSeg, row = w.s / nsw;
-    w.b = row / a.H;
-    w.i = row - w.b * a.H;
-    w.j = (w.s - row * nsw) * kSeg + (int)(threadIdx.x & 63) * 4;
-    w.n = min(4, a.W - w.j);
-    return true;
-}
-
-// the four fp32 of view v at the wave's place (its row is inside the plane), the leading n of them
-// (<= 0: none); the others read 0
-__device__ __forceinline__ f4 view_load4(const BackprojectArgs& a, const PlaneView& v, const float* image,
-                                         const Where& w, int n) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc(image, view_bytes(a.H, v.rs, a.W, 4));
-    return load4_f32(r, v.wide != 0, true, n, (unsigned)((long long)w.i * v.rs + w.j) * 4u);
-}
-
-// bit k: pixel j + k of row i is valid; z = the four depths (0 past the row)
-__device__ __forceinline__ unsigned valid4(const BackprojectArgs& a, const Where& w, f4& z) {
-    const unsigned in_row = w.n > 0 ? (1u << w.n) - 1u : 0u;
-    z = view_load4(a, a.depth, a.depth.image<float>(w.b), w, w.n);
-    unsigned m = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) m |= (unsigned)(z[k] > a.z_min && z[k] <= a.z_max) << k;
-    m &= in_row;
-    if (a.conf.base) {
-        const f4 c = view_load4(a, a.conf, a.conf.image<float>(w.b), w, w.n);
-        unsigned mc = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) mc |= (unsigned)(c[k] >= a.conf_min) << k;
-        m &= mc;
-    }
-    return m;
-}
-
-__device__ __forceinline__ Camera camera_of(const BackprojectArgs& a, int b) {
-    const float* k = a.k + (long long)b * a.kbs;
-    return Camera{k[0], k[4], k[2], k[5]};
-}
-
-// the point of pixel (i, j) at depth z: subtract, multiply, divide, one fp32 rounding each
-__device__ __forceinline__ void project(const Camera& c, int i, int j, float z, float& x, float& y) {
-#pragma clang fp contract(off)
-    const float u = (float)j - c.cx, v = (float)i - c.cy;
-    const float uz = u * z, vz = v * z;
-    x = uz / c.fx;
-    y = vz / c.fy;
-}
 
 // clamp(rintf(v), 0, 255); comparisons, so a NaN becomes 0
 __device__ __forceinline__ unsigned colour_q(float v) {

@@ -850,6 +850,50 @@ int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned ch
     return rc ? fail(rc, fn, why) : 0;
 }
 
+// nconv_normals_opts checked and turned into the kernels' arguments (NULL: all zero)
+static const char* normals_args(const nconv_normals_opts* o, nconv::NormalsArgs& n) {
+    n = nconv::NormalsArgs{};
+    if (!o) return nullptr;
+    if (!(o->jump_rel >= 0.f) || !(o->jump_abs >= 0.f)) return "jump_rel and jump_abs must be >= 0 (and not NaN)";
+    n.jump_rel = o->jump_rel, n.jump_abs = o->jump_abs;
+    n.gate = o->jump_rel != 0.f || o->jump_abs != 0.f;
+    n.empty = (unsigned)o->empty_rgb[0] | ((unsigned)o->empty_rgb[1] << 8) | ((unsigned)o->empty_rgb[2] << 16);
+    return nullptr;
+}
+
+int nconv_depth_normals(const nconv_backproject* d, const nconv_normals_opts* o, float* normals,
+                        unsigned char* image, void* stream) {
+    const char* fn = "nconv_depth_normals";
+    nconv::BackprojectArgs a;
+    nconv::NormalsArgs n;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (const char* why = normals_args(o, n)) return fail(-22, fn, why);
+    if (!normals && !image) return fail(-22, fn, "null normals and image: nothing to write");
+    if ((size_t)normals % 4) return fail(-22, fn, "normals not 4-byte aligned");
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_normals(a, n, normals, image, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
+int nconv_depth_normals_points(const nconv_backproject* d, const nconv_normals_opts* o, const int* index,
+                               const int* offsets, long long capacity, float* normals, void* stream) {
+    const char* fn = "nconv_depth_normals_points";
+    nconv::BackprojectArgs a;
+    nconv::NormalsArgs n;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (const char* why = normals_args(o, n)) return fail(-22, fn, why);
+    if (capacity < 0) return fail(-22, fn, "negative capacity");
+    if (capacity > 0 && (!index || !offsets || !normals)) return fail(-22, fn, "null index, offsets or normals");
+    if ((size_t)index % 4 || (size_t)offsets % 4 || (size_t)normals % 4)
+        return fail(-22, fn, "index / offsets / normals not 4-byte aligned");
+    if (capacity == 0) return 0;
+    // every row is below B * H * W < 2^31
+    const int cap = (int)(capacity < 0x7fffffffLL ? capacity : 0x7fffffffLL);
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_normals_points(a, n, index, offsets, cap, normals, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 size_t nconv_lidar_project_workspace_bytes(int B, int H, int W, int with_index) {
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
     return with_index ? (size_t)8 * B * H * W : 0;

@@ -291,6 +291,18 @@ int launch_backproject_map(const BackprojectArgs& a, float* xyz, hipStream_t st,
 int launch_backproject_points(const BackprojectArgs& a, float* xyz, unsigned char* rgb, int* index, int capacity,
                               int* offsets, int* ws, hipStream_t st, const char** why);
 
+// Surface normals of a depth map (nconv_depth_normals / _points), normals.hip; the sources are a
+// BackprojectArgs (its colour is not read).
+struct NormalsArgs {
+    float jump_rel, jump_abs;  // a neighbour is usable within jump_abs + jump_rel * z of the centre's depth
+    int gate;                  // 0: both are 0, every valid neighbour is usable
+    unsigned empty;            // the picture's pixel without a normal: R | G << 8 | B << 16
+};
+int launch_depth_normals(const BackprojectArgs& a, const NormalsArgs& o, float* normals, unsigned char* image,
+                         hipStream_t st, const char** why);
+int launch_depth_normals_points(const BackprojectArgs& a, const NormalsArgs& o, const int* index, const int* offsets,
+                                int capacity, float* normals, hipStream_t st, const char** why);
+
 // Projection of a LiDAR scan to the sparse depth plane (nconv_lidar_project), lidar_project.hip.
 struct LidarArgs {
     int B, H, W;

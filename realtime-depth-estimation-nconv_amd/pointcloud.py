@@ -8,10 +8,17 @@ crop, and DevicePrefetcher ships it with the frame. With it a completed depth ma
   backproject       the valid pixels compacted to a PointCloud (xyz, optional rgb and pixel index,
                     per-image offsets) in raster order, three launches and no host synchronisation
                     (nconv_backproject_points)
-  write_ply         points (and colours) as a binary little-endian PLY, on the host
+  normals           unit surface normals (B, 3, H, W) of the depth map on the image grid, NaN where a
+                    pixel has none; one launch (nconv_depth_normals, csrc/normals.hip)
+  normal_image      the camera-space normal picture (B, H, W, 3) uint8, ready for write_png8; the same
+                    launch, the fp32 map never reaches memory
+  write_ply         points (normals and colours) as a binary little-endian PLY, on the host
 
 A pixel is valid iff z > z_min and z <= z_max and (no conf or conf >= conf_min); its point is
 x = ((float)j - cx) * z / fx, y = ((float)i - cy) * z / fy, z: fp32, one rounding per operation.
+A normal is the normalised cross product of the vertical and the horizontal difference of the
+neighbouring points (central where both neighbours are valid and within jump_abs + jump_rel * z of the
+pixel's depth, one-sided where one is), turned towards the camera; include/nconv.h has the arithmetic.
 The confidence is the network's own (DNET.forward_with_confidence). Device tensors only: there is no
 PyTorch path.
 """
@@ -114,15 +121,69 @@ def backproject_map(depth, k, *, conf=None, conf_min=0.0, z_min=0.0, z_max=FLT_M
     return res
 
 
+def _normals_opts(jump_rel, jump_abs, empty=(0, 0, 0)):
+    from . import _lib
+    jump_rel, jump_abs = float(jump_rel), float(jump_abs)
+    if not (jump_rel >= 0.0 and jump_abs >= 0.0):
+        raise ValueError(f"pointcloud: jump_rel = {jump_rel} and jump_abs = {jump_abs} must be >= 0")
+    empty = tuple(int(c) for c in empty)
+    if len(empty) != 3 or not all(0 <= c <= 255 for c in empty):
+        raise ValueError(f"pointcloud: empty must be three values in 0..255, got {empty}")
+    o = _lib.NconvNormalsOpts()
+    o.jump_rel, o.jump_abs = jump_rel, jump_abs
+    o.empty_rgb[0], o.empty_rgb[1], o.empty_rgb[2] = empty
+    return o
+
+
+def _depth_normals(depth, k, conf, conf_min, z_min, z_max, jump_rel, jump_abs, empty, out, want_map, want_image):
+    from . import _lib
+    o = _normals_opts(jump_rel, jump_abs, empty)
+    d, (B, H, W) = _descriptor(depth, k, conf, conf_min, z_min, z_max)
+    nmap = _output(out, "normals", (B, 3, H, W), torch.float32, depth.device) if want_map else None
+    image = _output(out, "image", (B, H, W, 3), torch.uint8, depth.device) if want_image else None
+    rc = _lib.lib().nconv_depth_normals(ctypes.byref(d), ctypes.byref(o), None if nmap is None else _lib.ptr(nmap),
+                                        None if image is None else _lib.ptr(image), _lib.stream_handle(depth.device))
+    _lib.check(rc, "nconv_depth_normals")
+    return nmap, image
+
+
+def normals(depth, k, *, conf=None, conf_min=0.0, z_min=0.0, z_max=FLT_MAX, jump_rel=0.1, jump_abs=0.0, out=None):
+    """Unit surface normals (B, 3, H, W) fp32 of the depth map: planes nx, ny, nz in camera
+    coordinates, turned towards the camera (n . P <= 0), NaN in all three where the pixel has no
+    normal. depth, k, conf and the validity bounds as backproject_map takes them. A neighbour takes
+    part in a pixel's differences only where it is valid and its depth is within jump_abs + jump_rel * z
+    of the pixel's z (jump_rel = jump_abs = 0: every valid neighbour). out: an optional preallocated
+    result. One launch."""
+    return _depth_normals(depth, k, conf, conf_min, z_min, z_max, jump_rel, jump_abs, (0, 0, 0),
+                          None if out is None else {"normals": out}, True, False)[0]
+
+
+def normal_image(depth, k, *, conf=None, conf_min=0.0, z_min=0.0, z_max=FLT_MAX, jump_rel=0.1, jump_abs=0.0,
+                 empty=(0, 0, 0), out=None):
+    """The camera-space normal picture (B, H, W, 3) uint8 of the depth map, ready for write_png8:
+    R, G, B = nx, -ny, -nz mapped from [-1, 1] to 0..255, `empty` where the pixel has no normal. The
+    arguments are those of normals; the fp32 map is not written. One launch."""
+    return _depth_normals(depth, k, conf, conf_min, z_min, z_max, jump_rel, jump_abs, empty,
+                          None if out is None else {"image": out}, False, True)[1]
+
+
+def normals_and_image(depth, k, *, conf=None, conf_min=0.0, z_min=0.0, z_max=FLT_MAX, jump_rel=0.1, jump_abs=0.0,
+                      empty=(0, 0, 0), out=None):
+    """(normals, normal_image) of the depth map from one launch. out: an optional dict of
+    preallocated buffers 'normals' and 'image'."""
+    return _depth_normals(depth, k, conf, conf_min, z_min, z_max, jump_rel, jump_abs, empty, out, True, True)
+
+
 class PointCloud:
     """The result of backproject: device tensors at full capacity. xyz (capacity, 3) fp32; rgb
-    (capacity, 3) uint8 or None; index (capacity) int32 = (b * H + i) * W + j or None; offsets
+    (capacity, 3) uint8 or None; index (capacity) int32 = (b * H + i) * W + j or None; normals
+    (capacity, 3) fp32 unit normals, (0, 0, 0) where a point has none, or None; offsets
     (B + 1) int32: image b's points are rows [offsets[b], offsets[b + 1]) and offsets[B] is the true
     number of valid pixels. Rows from min(offsets[B], capacity) on are not written. Building one does
     not synchronise; count(), image(b) and truncated() read offsets on the host (once)."""
 
-    def __init__(self, xyz, rgb, index, offsets):
-        self.xyz, self.rgb, self.index, self.offsets = xyz, rgb, index, offsets
+    def __init__(self, xyz, rgb, index, offsets, normals=None):
+        self.xyz, self.rgb, self.index, self.offsets, self.normals = xyz, rgb, index, offsets, normals
         self._host = None
 
     @property
@@ -149,19 +210,30 @@ class PointCloud:
         return (self.xyz[lo:hi], None if self.rgb is None else self.rgb[lo:hi],
                 None if self.index is None else self.index[lo:hi])
 
+    def image_normals(self, b):
+        """The normals rows of image b, matching image(b); None without normals."""
+        o = self.host_offsets()
+        lo, hi = min(o[b], self.capacity), min(o[b + 1], self.capacity)
+        return None if self.normals is None else self.normals[lo:hi]
+
 
 def backproject(depth, k, *, conf=None, conf_min=0.0, color=None, reverse=False, z_min=0.0, z_max=FLT_MAX,
-                max_points=None, with_index=False, out=None):
+                max_points=None, with_index=False, normals=False, jump_rel=0.1, jump_abs=0.0, out=None):
     """The valid pixels of depth as a PointCloud, raster order inside an image, images in batch
     order, the same on every run. depth, conf, k as backproject_map takes them. color: fp32 planes
     (B, 3, H, W) (-> clamp(rint(v), 0, 255), NaN -> 0) or uint8 interleaved (B, H, W, 3), unit
     innermost stride; the point's three bytes keep the source's channel order, reversed with
     reverse=True. max_points: the capacity of the outputs (default B * H * W); points beyond it are
     dropped and PointCloud.truncated() tells. with_index: also the pixel index of every point.
-    out: an optional dict of preallocated contiguous buffers 'xyz', 'rgb', 'index', 'offsets',
-    'workspace' (uint8, workspace_bytes(B, H, W)) -- static buffers under hipGraph capture. Three
-    launches, no allocation when out is complete, no host synchronisation."""
+    normals: also every point's unit surface normal as the function normals defines it (jump_rel,
+    jump_abs: its gate), (0, 0, 0) where the pixel has none; a fourth launch
+    (nconv_depth_normals_points), which needs the index internally (PointCloud.index stays None
+    without with_index). out: an optional dict of preallocated contiguous buffers 'xyz', 'rgb', 'index',
+    'normals', 'offsets', 'workspace' (uint8, workspace_bytes(B, H, W)) -- static buffers under hipGraph
+    capture. Three launches (four with normals), no allocation when out is complete, no host
+    synchronisation."""
     from . import _lib
+    opts = _normals_opts(jump_rel, jump_abs) if normals else None
     d, (B, H, W) = _descriptor(depth, k, conf, conf_min, z_min, z_max)
     dev = depth.device
     if color is not None:
@@ -171,7 +243,8 @@ def backproject(depth, k, *, conf=None, conf_min=0.0, color=None, reverse=False,
         raise ValueError(f"pointcloud: max_points = {max_points} is negative")
     xyz = _output(out, "xyz", (cap, 3), torch.float32, dev)
     rgb = _output(out, "rgb", (cap, 3), torch.uint8, dev) if color is not None else None
-    index = _output(out, "index", (cap,), torch.int32, dev) if with_index else None
+    index = _output(out, "index", (cap,), torch.int32, dev) if with_index or normals else None
+    nrm = _output(out, "normals", (cap, 3), torch.float32, dev) if normals else None
     offsets = _output(out, "offsets", (B + 1,), torch.int32, dev)
     nws = workspace_bytes(B, H, W)
     ws = _output(out, "workspace", (nws,), torch.uint8, dev)
@@ -180,7 +253,11 @@ def backproject(depth, k, *, conf=None, conf_min=0.0, color=None, reverse=False,
         ctypes.byref(d), _lib.ptr(xyz) if cap else None, _lib.ptr(rgb) if cap else None,
         _lib.ptr(index) if cap else None, cap, _lib.ptr(offsets), _lib.ptr(ws), nws, _lib.stream_handle(dev))
     _lib.check(rc, "nconv_backproject_points")
-    return PointCloud(xyz, rgb, index, offsets)
+    if normals and cap:
+        rc = _lib.lib().nconv_depth_normals_points(ctypes.byref(d), ctypes.byref(opts), _lib.ptr(index),
+                                                   _lib.ptr(offsets), cap, _lib.ptr(nrm), _lib.stream_handle(dev))
+        _lib.check(rc, "nconv_depth_normals_points")
+    return PointCloud(xyz, rgb, index if with_index else None, offsets, nrm)
 
 
 def workspace_bytes(B, H, W):
@@ -193,28 +270,39 @@ def workspace_bytes(B, H, W):
     return n
 
 
-def write_ply(path, xyz, rgb=None):
-    """Points as a binary little-endian PLY: per vertex float x, y, z and, with rgb, uchar red,
-    green, blue. xyz (N, 3) float32, rgb (N, 3) uint8: host or device tensors or arrays, e.g.
-    PointCloud.image(b)[:2]. Host code (numpy)."""
+def write_ply(path, xyz, rgb=None, normals=None):
+    """Points as a binary little-endian PLY: per vertex float x, y, z, with normals float nx, ny,
+    nz, and with rgb uchar red, green, blue. xyz and normals (N, 3) float32, rgb (N, 3) uint8: host or
+    device tensors or arrays, e.g. PointCloud.image(b)[:2] and PointCloud.image_normals(b). Host code
+    (numpy)."""
     a = xyz.detach().cpu().numpy() if torch.is_tensor(xyz) else np.asarray(xyz)
     if a.ndim != 2 or a.shape[1] != 3 or a.dtype != np.float32:
         raise TypeError(f"pointcloud: write_ply takes float32 (N, 3) points, got {a.dtype} {a.shape}")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
-    c = None
+    c = nv = None
+    if normals is not None:
+        nv = normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)
+        if nv.shape != a.shape or nv.dtype != np.float32:
+            raise TypeError(f"pointcloud: write_ply takes float32 {a.shape} normals, got {nv.dtype} {nv.shape}")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if rgb is not None:
         c = rgb.detach().cpu().numpy() if torch.is_tensor(rgb) else np.asarray(rgb)
         if c.shape != a.shape or c.dtype != np.uint8:
             raise TypeError(f"pointcloud: write_ply takes uint8 {a.shape} colours, got {c.dtype} {c.shape}")
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-    rec = np.empty(a.shape[0], dtype=np.dtype(fields))  # packed: 12 or 15 bytes per vertex
+    rec = np.empty(a.shape[0], dtype=np.dtype(fields))  # packed: 12 or 15 bytes per vertex, 12 more with normals
     for n, name in enumerate("xyz"):
         rec[name] = a[:, n]
+    if nv is not None:
+        for n, name in enumerate(("nx", "ny", "nz")):
+            rec[name] = nv[:, n]
     if c is not None:
         for n, name in enumerate(("red", "green", "blue")):
             rec[name] = c[:, n]
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {a.shape[0]}",
             "property float x", "property float y", "property float z"]
+    if nv is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
     if c is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
     head.append("end_header")
