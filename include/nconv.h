@@ -839,6 +839,85 @@ int nconv_depth_normals(const nconv_backproject* d, const nconv_normals_opts* o,
 int nconv_depth_normals_points(const nconv_backproject* d, const nconv_normals_opts* o, const int* index,
                                const int* offsets, long long capacity, float* normals, void* stream);
 
+/* Added under ABI 27 (purely additive: two new entry points and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). A depth plane -> a random sparse subset of it with an exact
+ * number of samples per image: the training input of the reference (DataLoader_NYU.preprocess_depth:
+ * randperm, gather / scatter, mask) on the device, the "N random samples" protocol, and thinning a
+ * LiDAR plane to a budget. The result is a function of (input, seed, draw) alone: identical on every
+ * run and for every launch geometry. It does not reproduce torch.randperm's stream.
+ * For image b and pixel p = row * W + col (the logical pixel number, never a memory offset, so that a
+ * cropped view samples like its contiguous copy):
+ *   words      (w0, w1, w2, w3) = Philox4x32-10(counter = (p, b, draw, 0), key = (seed_lo, seed_hi))
+ *              (csrc/philox.h), with state = {seed_lo, seed_hi, draw} read from device memory: a
+ *              captured graph is replayed with a fresh draw by changing state[2]. A call never writes it.
+ *   candidate  iff (mask == NULL || mask byte != 0) && (all_pixels || (d > floor && d <= FLT_MAX)), d the
+ *              source value (comparisons: a NaN is no candidate). C_b: the candidates of image b.
+ *   target     n_b = C_b                                      NCONV_SPARSIFY_ALL
+ *                    min(n, C_b)                              NCONV_SPARSIFY_COUNT
+ *                    min(max(n_dev[b], 0), C_b)               NCONV_SPARSIFY_COUNT_DEV
+ *                    (int)floor((double)keep * (double)C_b)   NCONV_SPARSIFY_FRACTION
+ *   kept       the n_b candidates that are smallest under the order (w0 & key_mask, p). The pair is
+ *              unique, so the set is fully determined. key_mask is 0xffffffff in ordinary use; smaller
+ *              masks force ties onto p, and key_mask = 0 keeps the first n_b candidates in raster order.
+ *   noise      a kept pixel is noisy iff w1 < noise_threshold (0: no noise; for a share f of the kept
+ *              pixels the host passes floor(f * 2^32) clamped to [0, 2^32 - 1]). Then
+ *                u = (float)(w2 >> 8) * 2^-24,  s = 2 u - 1 (exact),  r = noise_amp * s,  t = d * r,
+ *                out = d + t
+ *              the last three one fp32 rounding each, no FMA: the reference's flat[idx] += flat[idx] *
+ *              noise. Where that result is a NaN (d not finite, with all_pixels) its sign and payload
+ *              are not specified. Noise is Bernoulli per pixel; the reference perturbs an exact count.
+ *   output     a kept pixel that is not noisy holds d bit for bit; every pixel that is not kept +0.0f.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_sparsify`
+ * or nconv_depth_sparsify_desc) */
+enum nconv_sparsify_mode {
+    NCONV_SPARSIFY_ALL = 0,
+    NCONV_SPARSIFY_COUNT = 1,
+    NCONV_SPARSIFY_COUNT_DEV = 2,
+    NCONV_SPARSIFY_FRACTION = 3
+};
+
+typedef struct nconv_depth_sparsify {
+    int B, H, W;
+    int mode;                       /* enum nconv_sparsify_mode                                   */
+    const float* src;               /* fp32 view: B planes of H rows of W, 4-byte aligned         */
+    long long src_image_stride;     /* elements; ignored when B == 1                              */
+    long long src_row_stride;       /* elements, >= W                                             */
+    const unsigned char* mask;      /* optional uint8 view; NULL: every pixel passes              */
+    long long mask_image_stride;    /* bytes; 0: one mask for the batch                           */
+    long long mask_row_stride;      /* bytes, >= W                                                */
+    const unsigned* state;          /* {seed_lo, seed_hi, draw} on the device, 4-byte aligned     */
+    const int* n_dev;               /* (B) int32 on the device: COUNT_DEV                         */
+    int n;                          /* COUNT, >= 0                                                */
+    float keep;                     /* FRACTION, 0 <= keep <= 1                                   */
+    int all_pixels;                 /* nonzero: floor is not applied (the reference's NYU rule)   */
+    float floor;                    /* candidate: d > floor                                       */
+    unsigned key_mask;              /* 0xffffffff; see `kept`                                     */
+    unsigned noise_threshold;       /* noisy: w1 < noise_threshold                                */
+    float noise_amp;                /* r = noise_amp * s                                          */
+} nconv_depth_sparsify_desc;
+
+/* Per image six 2048-bin digit histograms and six selection states. 0 for invalid sizes (B, H or
+ * W <= 0, B * H * W >= 2^31). */
+size_t nconv_depth_sparsify_workspace_bytes(int B, int H, int W);
+
+/* dst: fp32 view of B planes of H rows of W with its own strides in elements, overwritten entirely; it
+ * may be src itself (same pointer, same strides: in place), any other overlap of the two extents is
+ * refused. kept: optional (B) int32 = n_b. workspace: nconv_depth_sparsify_workspace_bytes(B, H, W)
+ * bytes, 8-byte aligned, overwritten; nothing in it is carried from one call to the next.
+ * Always eight kernels on `stream` whatever the data, the mode and n: one that zeroes the histograms,
+ * then the selection, a radix select over the 64-bit composite (w0 & key_mask) << 32 | p in six passes of
+ * 11, 11, 11, 11, 10 and 10 bits from the top (per-image histograms, private in LDS, merged with integer
+ * atomics: independent of the order of execution), each pass resolving the previous pass's bucket first,
+ * then the pass that writes dst. No host synchronisation, no allocation, no waiting between workgroups: capturable.
+ * -EINVAL before any launch for a NULL descriptor / src / dst / state, B, H or W <= 0,
+ * B * H * W >= 2^31, a row stride below W, images that overlap (an image stride below H * row stride;
+ * the mask's may be 0), an unknown mode, COUNT_DEV without n_dev, a negative n, keep outside [0, 1] or
+ * NaN, a workspace that is NULL, short or misaligned, src / dst / state / n_dev / kept not 4-byte
+ * aligned, and a dst that overlaps src without being src. */
+int nconv_depth_sparsify(const struct nconv_depth_sparsify* d, float* dst, long long dst_image_stride,
+                         long long dst_row_stride, int* kept, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,8 +19,9 @@ from . import lidar
 from .lidar import LidarProjector, kitti_projection, project_points, projection_from_k, read_velodyne_bin
 from . import visualize
 from .visualize import COLORMAPS, Colorizer, colorize, overlay, write_png8
+from .sparsify import Sparsifier, SparsifyBatch, sparsify
 
-__all__ = ["COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
+__all__ = ["Sparsifier", "SparsifyBatch", "sparsify", "COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
 "LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",
 "PointCloud", "backproject", "backproject_map", "write_ply", "normals", "normal_image", "normals_and_image","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",
            "SETP1_NCONV", "crop_hw", "SETP2_BP_EXPORT", "SETP2_BP_TRAIN", "RGBEncoder", "DepthMetrics",

@@ -37,6 +37,8 @@ FRAME_U8, FRAME_U16, FRAME_F32 = 0, 1, 2
 COLOR_NONE, COLOR_F32_PLANAR, COLOR_U8_INTERLEAVED = 0, 1, 2
 # nconv_depth_colorize.cmap_id
 CMAP_IDS = {"inferno": 0, "magma": 1, "viridis": 2, "turbo": 3, "gray": 4}
+# enum nconv_sparsify_mode
+SPARSIFY_ALL, SPARSIFY_COUNT, SPARSIFY_COUNT_DEV, SPARSIFY_FRACTION = 0, 1, 2, 3
 
 EXPORTED = (
     "nconv_abi_version",
@@ -88,6 +90,8 @@ EXPORTED = (
     "nconv_depth_colorize",
     "nconv_depth_normals",
     "nconv_depth_normals_points",
+    "nconv_depth_sparsify_workspace_bytes",
+    "nconv_depth_sparsify",
 )
 
 
@@ -186,6 +190,16 @@ class NconvDepthColorize(ctypes.Structure):
 
 class NconvNormalsOpts(ctypes.Structure):
     _fields_ = [("jump_rel", ctypes.c_float), ("jump_abs", ctypes.c_float), ("empty_rgb", ctypes.c_ubyte * 3)]
+
+
+class NconvDepthSparsify(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("mode", ctypes.c_int),
+                ("src", ctypes.c_void_p), ("src_image_stride", ctypes.c_longlong),
+                ("src_row_stride", ctypes.c_longlong), ("mask", ctypes.c_void_p),
+                ("mask_image_stride", ctypes.c_longlong), ("mask_row_stride", ctypes.c_longlong),
+                ("state", ctypes.c_void_p), ("n_dev", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("keep", ctypes.c_float), ("all_pixels", ctypes.c_int), ("floor", ctypes.c_float),
+                ("key_mask", ctypes.c_uint), ("noise_threshold", ctypes.c_uint), ("noise_amp", ctypes.c_float)]
 
 
 _lib = None
@@ -301,6 +315,10 @@ def _declare(lib):
     lib.nconv_depth_normals_points.restype = I
     lib.nconv_depth_normals_points.argtypes = [ctypes.POINTER(NconvBackproject), ctypes.POINTER(NconvNormalsOpts),
                                                P, P, L, P, P]
+    lib.nconv_depth_sparsify_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_depth_sparsify_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_depth_sparsify.restype = I
+    lib.nconv_depth_sparsify.argtypes = [ctypes.POINTER(NconvDepthSparsify), P, L, L, P, P, ctypes.c_size_t, P]
 
 
 def lib():

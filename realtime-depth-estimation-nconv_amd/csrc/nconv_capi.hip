@@ -977,4 +977,71 @@ int nconv_depth_colorize(const struct nconv_depth_colorize* d, unsigned char* ou
     return rc ? fail(rc, fn, why) : 0;
 }
 
+size_t nconv_depth_sparsify_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::sparsify_workspace_bytes(B);
+}
+
+// A view of B planes of H rows of W elements read through 64-bit offsets: NULL, or why it is refused.
+// zero_bs: an image stride of 0 shares one plane among the images.
+static const char* sparsify_view(const char* name, int B, int H, int W, long long bs, long long rs, bool zero_bs,
+                                 std::string& text) {
+    const char* why = nullptr;
+    if (rs < W) why = "row stride smaller than W";
+    else if (rs > (1LL << 40) || bs > (1LL << 40)) why = "stride too large";
+    else if (B > 1 && !(zero_bs && bs == 0) && bs < H * rs) why = "image stride smaller than H * row stride";
+    if (!why) return nullptr;
+    text = std::string(name) + ": " + why;
+    return text.c_str();
+}
+
+int nconv_depth_sparsify(const struct nconv_depth_sparsify* d, float* dst, long long dst_image_stride,
+                         long long dst_row_stride, int* kept, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    const char* fn = "nconv_depth_sparsify";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !dst) return fail(-22, fn, "null src or dst");
+    if (!d->state) return fail(-22, fn, "null state");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->mode < NCONV_SPARSIFY_ALL || d->mode > NCONV_SPARSIFY_FRACTION)
+        return fail(-22, fn, "unknown mode (enum nconv_sparsify_mode)");
+    if (d->mode == NCONV_SPARSIFY_COUNT_DEV && !d->n_dev) return fail(-22, fn, "COUNT_DEV without n_dev");
+    if (d->n < 0) return fail(-22, fn, "negative n");
+    if (!(d->keep >= 0.f && d->keep <= 1.f))
+        return fail(-22, fn, "keep must be in [0, 1] (and not NaN)");
+    std::string text;
+    if (const char* why = sparsify_view("src", B, H, W, d->src_image_stride, d->src_row_stride, false, text))
+        return fail(-22, fn, why);
+    if (const char* why = sparsify_view("dst", B, H, W, dst_image_stride, dst_row_stride, false, text))
+        return fail(-22, fn, why);
+    if (d->mask)
+        if (const char* why = sparsify_view("mask", B, H, W, d->mask_image_stride, d->mask_row_stride, true, text))
+            return fail(-22, fn, why);
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)d->state % 4 || (size_t)d->n_dev % 4 || (size_t)kept % 4)
+        return fail(-22, fn, "src / dst / state / n_dev / kept not 4-byte aligned");
+    if (!workspace || workspace_bytes < nconv::sparsify_workspace_bytes(B)) return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    const long long sbs = B > 1 ? d->src_image_stride : 0, dbs = B > 1 ? dst_image_stride : 0;
+    const bool same = dst == d->src && dst_row_stride == d->src_row_stride && dbs == sbs;
+    if (!same) {  // the byte extents of the two views must be disjoint
+        const char *s0 = (const char*)d->src, *d0 = (const char*)dst;
+        const char* s1 = s0 + ((B - 1) * sbs + (long long)(H - 1) * d->src_row_stride + W) * 4;
+        const char* d1 = d0 + ((B - 1) * dbs + (long long)(H - 1) * dst_row_stride + W) * 4;
+        if (s0 < d1 && d0 < s1) return fail(-22, fn, "dst overlaps src without being src (same pointer and strides)");
+    }
+    nconv::SparsifyArgs a{};
+    a.B = B, a.H = H, a.W = W, a.mode = d->mode;
+    a.src = d->src, a.sbs = sbs, a.srs = d->src_row_stride;
+    a.mask = d->mask, a.mbs = B > 1 ? d->mask_image_stride : 0, a.mrs = d->mask_row_stride;
+    a.state = d->state, a.n_dev = d->n_dev, a.n = d->n, a.keep = d->keep;
+    a.all_pixels = d->all_pixels != 0, a.floor = d->floor;
+    a.key_mask = d->key_mask, a.noise_threshold = d->noise_threshold, a.noise_amp = d->noise_amp;
+    a.dst = dst, a.dbs = dbs, a.drs = dst_row_stride, a.kept = kept;
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_sparsify(a, workspace, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

@@ -335,4 +335,34 @@ struct ColorizeArgs {
 };
 int launch_depth_colorize(const ColorizeArgs& a, hipStream_t st, const char** why);
 
+// Exact-count random subset of a depth plane (nconv_depth_sparsify), sparsify.hip.
+struct SparsifySel {
+    unsigned long long prefix;  // the digits of the threshold key resolved so far, from the top
+    unsigned rank;              // 0-based rank of the threshold among the candidates under that prefix
+    int n;                      // n_b
+};
+struct SparsifyArgs {
+    int B, H, W;
+    int mode;                     // enum nconv_sparsify_mode
+    const float* src;             // strides in elements (64-bit offsets: no limit on the extent)
+    long long sbs, srs;
+    const unsigned char* mask;    // null: none; strides in bytes, mbs 0: one mask for the batch
+    long long mbs, mrs;
+    const unsigned* state;        // seed_lo, seed_hi, draw
+    const int* n_dev;
+    int n;
+    float keep;
+    int all_pixels;
+    float floor;
+    unsigned key_mask, noise_threshold;
+    float noise_amp;
+    float* dst;                   // may be src with the same strides
+    long long dbs, drs;
+    int* kept;                    // null: skip
+    unsigned* hist;               // [pass][image][bin]
+    SparsifySel* sel;             // [pass][image]
+};
+size_t sparsify_workspace_bytes(int B);
+int launch_depth_sparsify(SparsifyArgs a, void* workspace, hipStream_t st, const char** why);
+
 }  // namespace nconv

@@ -206,9 +206,17 @@ class DataLoader_KITTI_test(DataLoader_KITTI_seltest):
 class DataLoader_NYU(Dataset):
     """NYU-v2 .npy split (nyuloader.py:10-119). The sparse input is the ground truth times a random
     mask (use_mask) or with as many random points zeroed as the mask has zeros, optionally with
-    +-10 % noise on 10 % of the points (add_noise), exactly as the reference."""
+    +-10 % noise on 10 % of the points (add_noise), exactly as the reference.
+    sparse="device" leaves that derivation to sparsify.SparsifyBatch on the GPU: the sample's 'depth' is
+    the cropped ground truth and it carries 'mask' (uint8, the mask file cropped alike; use_mask) or
+    'n_keep' (int32: H * W minus the cropped mask's zeros). No randperm runs on the host; add_noise is
+    then the batch stage's argument."""
 
-    def __init__(self, data_dir, mode, use_mask, add_noise, height=480, width=640, tp_min=50, raw=False):
+    def __init__(self, data_dir, mode, use_mask, add_noise, height=480, width=640, tp_min=50, raw=False,
+                 sparse="host"):
+        if sparse not in ("host", "device"):
+            raise ValueError(f"sparse must be 'host' or 'device', got {sparse!r}")
+        self.sparse = sparse
         self.depth_path = os.path.join(data_dir, mode, "gt")
         self.lidar_path = os.path.join(data_dir, mode, "depth")
         self.rgb_path = os.path.join(data_dir, mode, "img")
@@ -245,6 +253,14 @@ class DataLoader_NYU(Dataset):
         gt = gt[:, tp:tp + self.height, lp:lp + self.width]
         k[0, 2] -= lp
         k[1, 2] -= tp
+        if self.sparse == "device":
+            mask = self.load_mask()[tp:tp + self.height, lp:lp + self.width] != 0
+            sample = {"rgb": rgb, "depth": gt.clone(), "gt": gt, "k": k}
+            if self.use_mask:
+                sample["mask"] = torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8))[None]
+            else:
+                sample["n_keep"] = torch.tensor(int(np.count_nonzero(mask)), dtype=torch.int32)
+            return sample
         depth = self.preprocess_depth(self.depths[index], self.use_mask, self.add_noise)
         return {"rgb": rgb, "depth": depth, "gt": gt, "k": k}
 
@@ -259,13 +275,16 @@ class DataLoader_NYU(Dataset):
 
     get_gt = get_depth
 
-    def preprocess_depth(self, depth_path, apply_mask, apply_noise):
-        raw_depth = self.get_depth(depth_path)
+    def load_mask(self):
+        """A random mask file as a (480, 640) array (resized with PIL NEAREST when it is not)."""
         mask_raw = np.load(random.choice(self.masks), allow_pickle=False)
         if mask_raw.shape != (480, 640):
-            mask = np.array(Image.fromarray(mask_raw).resize((640, 480), Image.NEAREST))
-        else:
-            mask = mask_raw
+            return np.array(Image.fromarray(mask_raw).resize((640, 480), Image.NEAREST))
+        return mask_raw
+
+    def preprocess_depth(self, depth_path, apply_mask, apply_noise):
+        raw_depth = self.get_depth(depth_path)
+        mask = self.load_mask()
         if apply_noise:
             n = raw_depth.numel()
             nn_ = int(n * 0.1)
