@@ -918,6 +918,67 @@ int nconv_depth_sparsify(const struct nconv_depth_sparsify* d, float* dst, long 
                          long long dst_row_stride, int* kept, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* Added under ABI 27 (purely additive: one new entry point and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). Occluded LiDAR returns taken out of a sparse depth plane.
+ * The scanner does not sit where the camera sits (KITTI: about 8 cm above and 27 cm behind cam0), so
+ * beside every foreground silhouette the projected scan holds background returns the camera cannot
+ * see, between the foreground returns. nconv_lidar_project resolves collisions on one pixel only, and
+ * KITTI's velodyne_raw PNGs hold such returns too. The remedy is the usual local window test: a return
+ * is dropped when enough clearly nearer returns lie next to it.
+ * Every arithmetic operation below is one fp32 rounding in the stated order, no FMA contraction. For
+ * image b and pixel p = (i, j) with value v_p:
+ *   valid(p)    v_p is finite and v_p > floor (floor = -INFINITY: every finite value is valid); the
+ *               "empty" rule of nconv_depth_colorize
+ *   lim(q)      = v_q + (jump_abs + jump_rel * v_q)       (one multiply, two adds), for valid q
+ *   window(p)   the pixels q != p with |i_q - i_p| <= rh and |j_q - j_p| <= rw that lie inside the
+ *               image: the window is clipped at the border, and a pixel outside the image is no
+ *               candidate whatever floor is
+ *   support(p)  the number of valid q of window(p) with v_p > lim(q)   (a strict float comparison: a
+ *               NaN or +inf lim supports nothing)
+ *   removed(p)  valid(p) && support(p) >= min_support
+ *   dst[p]      v_p bit for bit where p is valid and not removed, +0.0f everywhere else (removed,
+ *               empty and non-finite pixels)
+ * rh = rw = 0 removes nothing; a min_support larger than the window is legal and removes nothing. The
+ * result is a function of the input alone: identical on every run. The source is only read.
+ * What the rule cannot avoid: a visible background return just outside a silhouette has nearer returns
+ * in its window too and is dropped as well; on the road surface a tall window with a small jump_abs /
+ * jump_rel removes far ground returns in favour of the nearer scan line below them; min_support > 1
+ * keeps one stray near return (dust, rain) from clearing a window of good ones. Nobody has measured
+ * parameter values on KITTI.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_occlusion`
+ * or nconv_depth_occlusion_desc) */
+typedef struct nconv_depth_occlusion {
+    int B, H, W;
+    int rh, rw;                     /* window half-heights / half-widths, 0 .. 16 (up to 33 x 33)  */
+    int min_support;                /* >= 1                                                        */
+    const float* src;               /* fp32 view: B planes of H rows of W, 4-byte aligned          */
+    long long src_image_stride;     /* elements; ignored when B == 1                               */
+    long long src_row_stride;       /* elements, >= W                                              */
+    float jump_abs, jump_rel;       /* >= 0, not NaN                                               */
+    float floor;                    /* valid: v > floor; not NaN                                   */
+} nconv_depth_occlusion_desc;
+
+/* dst: fp32 view of B planes of H rows of W with its own strides in elements, overwritten entirely.
+ * It must not overlap src: neighbours are read, so there is no in-place operation, and the host
+ * compares the two byte extents. Optional outputs (NULL: skip):
+ *   removed  (B, H, W) contiguous uint8, 1 where the pixel is removed and 0 elsewhere, written entirely
+ *   index    (B, H, W) contiguous int32, updated in place: -1 where the pixel is removed or not valid,
+ *            left alone elsewhere. The index plane of nconv_lidar_project, so that the caller can name
+ *            the scan rows that were dropped.
+ *   counts   (B, 2) int32 = {valid pixels, removed pixels} of every image (integer atomics: the same
+ *            on every run)
+ * One kernel on `stream`, preceded by one small kernel that zeroes counts when counts is given. No
+ * workspace, no host synchronisation, no allocation, no waiting between workgroups: capturable. No
+ * byte outside the source view's extent is read. A workgroup stages a 32 x 64 tile with its halo in
+ * LDS, lists the tile's valid pixels and shares each one's window across lanes.
+ * -EINVAL before any launch for a NULL descriptor / src / dst, B, H or W <= 0, B * H * W >= 2^31, rh or
+ * rw outside 0..16, a negative or NaN jump_abs or jump_rel, a NaN floor, min_support < 1, src / dst /
+ * index / counts not 4-byte aligned, a src or dst view whose strides are smaller than its rows /
+ * images or whose image spans 2^31 bytes or more, and a dst whose extent overlaps src's. */
+int nconv_depth_occlusion(const struct nconv_depth_occlusion* d, float* dst, long long dst_image_stride,
+                          long long dst_row_stride, unsigned char* removed, int* index, int* counts,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,7 @@ EXPORTED = (
     "nconv_depth_normals_points",
     "nconv_depth_sparsify_workspace_bytes",
     "nconv_depth_sparsify",
+    "nconv_depth_occlusion",
 )
 
 
@@ -200,6 +201,13 @@ class NconvDepthSparsify(ctypes.Structure):
                 ("state", ctypes.c_void_p), ("n_dev", ctypes.c_void_p), ("n", ctypes.c_int),
                 ("keep", ctypes.c_float), ("all_pixels", ctypes.c_int), ("floor", ctypes.c_float),
                 ("key_mask", ctypes.c_uint), ("noise_threshold", ctypes.c_uint), ("noise_amp", ctypes.c_float)]
+
+
+class NconvDepthOcclusion(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("rh", ctypes.c_int),
+                ("rw", ctypes.c_int), ("min_support", ctypes.c_int), ("src", ctypes.c_void_p),
+                ("src_image_stride", ctypes.c_longlong), ("src_row_stride", ctypes.c_longlong),
+                ("jump_abs", ctypes.c_float), ("jump_rel", ctypes.c_float), ("floor", ctypes.c_float)]
 
 
 _lib = None
@@ -319,6 +327,8 @@ def _declare(lib):
     lib.nconv_depth_sparsify_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_depth_sparsify.restype = I
     lib.nconv_depth_sparsify.argtypes = [ctypes.POINTER(NconvDepthSparsify), P, L, L, P, P, ctypes.c_size_t, P]
+    lib.nconv_depth_occlusion.restype = I
+    lib.nconv_depth_occlusion.argtypes = [ctypes.POINTER(NconvDepthOcclusion), P, L, L, P, P, P, P]
 
 
 def lib():

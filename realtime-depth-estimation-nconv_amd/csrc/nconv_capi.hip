@@ -1044,4 +1044,42 @@ int nconv_depth_sparsify(const struct nconv_depth_sparsify* d, float* dst, long 
     return rc ? fail(rc, fn, why) : 0;
 }
 
+int nconv_depth_occlusion(const struct nconv_depth_occlusion* d, float* dst, long long dst_image_stride,
+                          long long dst_row_stride, unsigned char* removed, int* index, int* counts,
+                          void* stream) {
+    const char* fn = "nconv_depth_occlusion";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !dst) return fail(-22, fn, "null src or dst");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->rh < 0 || d->rh > 16 || d->rw < 0 || d->rw > 16) return fail(-22, fn, "rh and rw must be in [0, 16]");
+    if (!(d->jump_abs >= 0.f) || !(d->jump_rel >= 0.f)) return fail(-22, fn, "jump_abs or jump_rel is negative or NaN");
+    if (d->floor != d->floor) return fail(-22, fn, "floor is NaN");
+    if (d->min_support < 1) return fail(-22, fn, "min_support must be at least 1");
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)index % 4 || (size_t)counts % 4)
+        return fail(-22, fn, "src / dst / index / counts not 4-byte aligned");
+    nconv::OcclusionArgs a{};
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(d->src, B, H, W, 4, d->src_image_stride, d->src_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.s))
+        return fail(-22, fn, (std::string("src: ") + why).c_str());
+    nconv::PlaneView dv{};
+    if (const char* why = view_args(dst, B, H, W, 4, dst_image_stride, dst_row_stride, kNoStrideLimit, 16, kViewPoints, dv))
+        return fail(-22, fn, (std::string("dst: ") + why).c_str());
+    {  // neighbours are read: the byte extents of the two views must be disjoint
+        const char *s0 = (const char*)d->src, *d0 = (const char*)dst;
+        const char* s1 = s0 + ((B - 1) * a.s.bs + (long long)(H - 1) * a.s.rs + W) * 4;
+        const char* d1 = d0 + ((B - 1) * dv.bs + (long long)(H - 1) * dv.rs + W) * 4;
+        if (s0 < d1 && d0 < s1) return fail(-22, fn, "dst overlaps src (no in-place operation: neighbours are read)");
+    }
+    a.rh = d->rh, a.rw = d->rw, a.min_support = d->min_support;
+    a.jump_abs = d->jump_abs, a.jump_rel = d->jump_rel, a.floor = d->floor;
+    a.dst = dst, a.dbs = dv.bs, a.drs = dv.rs;
+    a.removed = removed, a.index = index, a.counts = counts;
+    const char* why = nullptr;
+    int rc = nconv::launch_depth_occlusion(a, (hipStream_t)stream, &why);
+    return rc ? fail(rc, fn, why) : 0;
+}
+
 }  // extern "C"

@@ -365,4 +365,19 @@ struct SparsifyArgs {
 size_t sparsify_workspace_bytes(int B);
 int launch_depth_sparsify(SparsifyArgs a, void* workspace, hipStream_t st, const char** why);
 
+// Occluded LiDAR returns removed from a sparse depth plane (nconv_depth_occlusion), occlusion.hip.
+struct OcclusionArgs {
+    PlaneView s;              // fp32, strides in elements
+    int B, H, W;
+    int rh, rw;               // 0 .. 16
+    int min_support;
+    float jump_abs, jump_rel, floor;
+    float* dst;               // strides in elements; disjoint from the source
+    long long dbs, drs;
+    unsigned char* removed;   // (B, H, W) contiguous, or null
+    int* index;               // (B, H, W) contiguous, updated in place, or null
+    int* counts;              // (B, 2), or null
+};
+int launch_depth_occlusion(const OcclusionArgs& a, hipStream_t st, const char** why);
+
 }  // namespace nconv
