@@ -979,6 +979,108 @@ int nconv_depth_occlusion(const struct nconv_depth_occlusion* d, float* dst, lon
                           long long dst_row_stride, unsigned char* removed, int* index, int* counts,
                           void* stream);
 
+/* Added under ABI 27 (purely additive: one new entry point and two new structs, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). The training augmentation of a depth-completion batch: one
+ * random crop window and one horizontal flip per image, applied alike to every tensor of the batch, the
+ * intrinsics rewritten to match, photometric jitter on the RGB, and a report of what was drawn. These
+ * are not torchvision's ColorJitter semantics: contrast pivots on a constant, not on the image mean,
+ * and there is no hue. No resampling of any kind: sparse depth cannot be interpolated honestly.
+ * Sources (each optional; all of source size (H, W), batch B, unit-stride rows, strides in elements
+ * unless stated): rgb fp32 (B, 3, H, W) with image, channel and row strides; plane[0..2] fp32
+ * single-channel planes (sparse depth, ground truth, one spare) with image and row strides; mask uint8
+ * (B, H, W) with strides in bytes and no alignment requirement, image stride 0: one mask for the batch;
+ * k fp32 (B, 3, 3) contiguous. Outputs: contiguous tensors of the output size (h, w), 1 <= h <= H and
+ * 1 <= w <= W ((B, 3, h, w), (B, h, w)), each overwritten entirely; k_out (B, 3, 3); optional params
+ * (B, 4) int32 {y0, x0, flip, 0}; optional gains (B, 5) fp32 {g_b, g_c, gain_0, gain_1, gain_2}.
+ * For image b:
+ *   words      (w0, w1, w2, w3) = Philox4x32-10(counter = (b, 0, draw, 1), key = (seed_lo, seed_hi))
+ *              (j0, j1, j2, j3) = Philox4x32-10(counter = (b, 1, draw, 1), key = (seed_lo, seed_hi))
+ *              (csrc/philox.h), state = {seed_lo, seed_hi, draw} read from device memory and never
+ *              written by the call. The last counter word 1 keeps these streams apart from
+ *              nconv_depth_sparsify's (p, b, draw, 0).
+ *   window     per axis its own mode; y0 from (mode_y, w0, H, h), x0 alike from (mode_x, w1, W, w):
+ *                NCONV_AUGMENT_RANDOM   (uint32)(((uint64)w0 * (uint64)(H - h + 1)) >> 32)
+ *                NCONV_AUGMENT_CENTER   (H - h) / 2, integer division
+ *                NCONV_AUGMENT_MIN      0
+ *                NCONV_AUGMENT_MAX      H - h (KITTI's "keep the bottom rows")
+ *   flip       (uint64)w2 < flip_threshold, flip_threshold in 0 .. 2^32: for a probability p the host
+ *              passes floor(p * 2^32) clamped to that range, so 0 never flips and 2^32 always flips.
+ *   geometry   out[b][..][i][j] = src[b][..][y0 + i][flip ? x0 + (w - 1 - j) : x0 + j] for every plane,
+ *              the mask and the RGB channels: a bit-for-bit copy, NaNs and payloads included. No byte
+ *              outside a source view's extent is read.
+ *   intrinsics each operation one fp32 rounding:
+ *                cx1 = k[0][2] - (float)x0,  cy1 = k[1][2] - (float)y0
+ *                k_out[0][2] = flip ? (float)(w - 1) - cx1 : cx1,  k_out[1][2] = cy1
+ *              and the other seven entries copied bit for bit.
+ *   jitter     RGB only, and skipped entirely when brightness == contrast == color == 0: the RGB is then
+ *              a bit-for-bit copy without a clamp and the gains are reported as 1. Otherwise, with
+ *              u(x) = (float)(x >> 8) * 2^-24 and s(x) = 2 u(x) - 1 (both exact),
+ *                g_b = 1 + brightness * s(j0),  g_c = 1 + contrast * s(j1),
+ *                gain_0 = 1 + color * s(w3),  gain_1 = 1 + color * s(j2),  gain_2 = 1 + color * s(j3)
+ *              (one multiply and one add each), and for a value v of channel plane c, in this order, one
+ *              fp32 rounding per operation and no FMA contraction:
+ *                a = v * g_b;  a = a * gain_c;  a = a - pivot;  a = a * g_c;  a = a + pivot;
+ *                out = fminf(fmaxf(a, 0.0f), rgb_max)
+ *              the clamp made by comparisons (a > 0 ? a : 0, then a < rgb_max ? a : rgb_max), so that
+ *              -0.0 comes out as +0.0. A NaN v with jitter on gives an unspecified result. The usual
+ *              values are pivot = 127.5 and rgb_max = 255.
+ * The result is a function of (inputs, seed, draw) alone: identical on every run and for every launch
+ * geometry. csrc/augment_params.h holds the draw as code a host program can compile.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_frame_augment`
+ * or nconv_frame_augment_desc) */
+enum nconv_augment_crop {
+    NCONV_AUGMENT_RANDOM = 0,
+    NCONV_AUGMENT_CENTER = 1,
+    NCONV_AUGMENT_MIN = 2,
+    NCONV_AUGMENT_MAX = 3
+};
+
+typedef struct nconv_augment_plane {
+    const float* src;               /* NULL: absent; fp32 view, 4-byte aligned                     */
+    long long image_stride;         /* elements; ignored when B == 1                               */
+    long long row_stride;           /* elements, >= W                                              */
+    float* out;                     /* (B, 1, h, w) contiguous                                     */
+} nconv_augment_plane;
+
+typedef struct nconv_frame_augment {
+    int B, H, W;                    /* batch and source size                                       */
+    int h, w;                       /* output size                                                 */
+    int mode_y, mode_x;             /* enum nconv_augment_crop                                     */
+    unsigned long long flip_threshold; /* 0 .. 2^32                                                */
+    const unsigned* state;          /* {seed_lo, seed_hi, draw} on the device, 4-byte aligned      */
+    const float* rgb;               /* NULL: absent; fp32 (B, 3, H, W) view                        */
+    long long rgb_image_stride;     /* elements; ignored when B == 1                               */
+    long long rgb_channel_stride;   /* elements                                                    */
+    long long rgb_row_stride;       /* elements, >= W                                              */
+    float* rgb_out;                 /* (B, 3, h, w) contiguous                                     */
+    nconv_augment_plane plane[3];
+    const unsigned char* mask;      /* NULL: absent; uint8 view, any alignment                     */
+    long long mask_image_stride;    /* bytes; 0: one mask for the batch                            */
+    long long mask_row_stride;      /* bytes, >= W                                                 */
+    unsigned char* mask_out;        /* (B, 1, h, w) contiguous                                     */
+    const float* k;                 /* NULL: absent; (B, 3, 3) contiguous                          */
+    float* k_out;                   /* (B, 3, 3)                                                   */
+    int* params;                    /* optional (B, 4) {y0, x0, flip, 0}                           */
+    float* gains;                   /* optional (B, 5) {g_b, g_c, gain_0, gain_1, gain_2}          */
+    float brightness, contrast, color; /* amplitudes in [0, 1]                                     */
+    float pivot, rgb_max;           /* 127.5 and 255 in ordinary use                               */
+} nconv_frame_augment_desc;
+
+/* One kernel on `stream` for every tensor of the batch: the grid's z dimension enumerates images, y the
+ * tensor slots (each RGB channel, each plane, the mask) and x groups of four output pixels of a row, so
+ * the draw of an image is uniform over a workgroup. A lane stores its four pixels as 16 bytes where the
+ * address allows, reads its four source pixels (reversed under a flip) at their 4-byte alignment, and
+ * the first workgroup of an image writes k_out, params and gains. No workspace, no atomics, no host
+ * synchronisation, no allocation, no waiting between workgroups: capturable.
+ * -EINVAL before any launch for a NULL descriptor or state; no source at all; a source without its
+ * output or an output without its source (k without k_out included); B, H, W, h or w <= 0; h > H or
+ * w > W; B * 3 * H * W >= 2^31; a row stride below W, or images or channels that overlap (an image stride
+ * below the image's extent, a channel stride below H * row stride; the mask's image stride may be 0);
+ * an unknown mode; flip_threshold > 2^32; an amplitude that is NaN or outside [0, 1]; a NaN pivot or
+ * rgb_max, or rgb_max < 0; fp32 / int32 pointers or state not 4-byte aligned; and any output extent
+ * that overlaps a source extent (state counts as a source). */
+int nconv_frame_augment(const struct nconv_frame_augment* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

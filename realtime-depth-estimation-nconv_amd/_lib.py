@@ -39,6 +39,8 @@ COLOR_NONE, COLOR_F32_PLANAR, COLOR_U8_INTERLEAVED = 0, 1, 2
 CMAP_IDS = {"inferno": 0, "magma": 1, "viridis": 2, "turbo": 3, "gray": 4}
 # enum nconv_sparsify_mode
 SPARSIFY_ALL, SPARSIFY_COUNT, SPARSIFY_COUNT_DEV, SPARSIFY_FRACTION = 0, 1, 2, 3
+# enum nconv_augment_crop
+AUGMENT_CROPS = {"random": 0, "center": 1, "min": 2, "max": 3}
 
 EXPORTED = (
     "nconv_abi_version",
@@ -93,6 +95,7 @@ EXPORTED = (
     "nconv_depth_sparsify_workspace_bytes",
     "nconv_depth_sparsify",
     "nconv_depth_occlusion",
+    "nconv_frame_augment",
 )
 
 
@@ -208,6 +211,25 @@ class NconvDepthOcclusion(ctypes.Structure):
                 ("rw", ctypes.c_int), ("min_support", ctypes.c_int), ("src", ctypes.c_void_p),
                 ("src_image_stride", ctypes.c_longlong), ("src_row_stride", ctypes.c_longlong),
                 ("jump_abs", ctypes.c_float), ("jump_rel", ctypes.c_float), ("floor", ctypes.c_float)]
+
+
+class NconvAugmentPlane(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("image_stride", ctypes.c_longlong), ("row_stride", ctypes.c_longlong),
+                ("out", ctypes.c_void_p)]
+
+
+class NconvFrameAugment(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
+                ("w", ctypes.c_int), ("mode_y", ctypes.c_int), ("mode_x", ctypes.c_int),
+                ("flip_threshold", ctypes.c_ulonglong), ("state", ctypes.c_void_p), ("rgb", ctypes.c_void_p),
+                ("rgb_image_stride", ctypes.c_longlong), ("rgb_channel_stride", ctypes.c_longlong),
+                ("rgb_row_stride", ctypes.c_longlong), ("rgb_out", ctypes.c_void_p),
+                ("plane", NconvAugmentPlane * 3), ("mask", ctypes.c_void_p),
+                ("mask_image_stride", ctypes.c_longlong), ("mask_row_stride", ctypes.c_longlong),
+                ("mask_out", ctypes.c_void_p), ("k", ctypes.c_void_p), ("k_out", ctypes.c_void_p),
+                ("params", ctypes.c_void_p), ("gains", ctypes.c_void_p), ("brightness", ctypes.c_float),
+                ("contrast", ctypes.c_float), ("color", ctypes.c_float), ("pivot", ctypes.c_float),
+                ("rgb_max", ctypes.c_float)]
 
 
 _lib = None
@@ -329,6 +351,8 @@ def _declare(lib):
     lib.nconv_depth_sparsify.argtypes = [ctypes.POINTER(NconvDepthSparsify), P, L, L, P, P, ctypes.c_size_t, P]
     lib.nconv_depth_occlusion.restype = I
     lib.nconv_depth_occlusion.argtypes = [ctypes.POINTER(NconvDepthOcclusion), P, L, L, P, P, P, P]
+    lib.nconv_frame_augment.restype = I
+    lib.nconv_frame_augment.argtypes = [ctypes.POINTER(NconvFrameAugment), P]
 
 
 def lib():

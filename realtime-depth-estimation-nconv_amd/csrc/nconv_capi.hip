@@ -131,6 +131,8 @@ LayerDev make_dev(const nconv_layer* L) {
 
 }  // namespace
 
+int nconv::capi_fail(int code, const char* fn, const char* why) { return fail(code, fn, why); }
+
 extern "C" {
 
 int nconv_abi_version(void) { return NCONV_ABI_VERSION; }

@@ -380,4 +380,8 @@ struct OcclusionArgs {
 };
 int launch_depth_occlusion(const OcclusionArgs& a, hipStream_t st, const char** why);
 
+// Records "<fn>: <why>" as the calling thread's nconv_last_error() text and returns code: for an entry
+// point that lives beside its kernel (nconv_frame_augment, augment.hip). Defined in nconv_capi.hip.
+int capi_fail(int code, const char* fn, const char* why);
+
 }  // namespace nconv
