@@ -1,5 +1,6 @@
 """Argument checks shared by the modules that hand tensors to libnconv's I/O entry points
-(metrics, frames, pointcloud, lidar): what a strided view of planes is on the Python side.
+(metrics, frames, pointcloud, lidar, visualize, sparsify, occlusion): what a strided view of planes
+is on the Python side.
 
 Every helper takes the calling module's `prefix` ("frames", "depth metrics", ...), so the text of an
 exception names the module the caller used.
@@ -63,3 +64,20 @@ def output(out, key, shape, dtype, device, prefix, source="source"):
     if t.device != device:
         raise RuntimeError(f"{prefix}: out[{key!r}] on {t.device}, the {source} on {device}")
     return t
+
+
+def dest_plane(out, key, B, H, W, device, prefix, source="source"):
+    """(tensor, image stride, row stride in elements) of the fp32 destination out[key], any (B, 1, H, W)
+    view of unit-stride rows on device, or of a new contiguous tensor where out has none."""
+    t = None if out is None else out.get(key)
+    if t is None:
+        t = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
+    else:
+        require_tensor(t, f"out[{key!r}]", (torch.float32,), prefix)
+        if t.device != device:
+            raise RuntimeError(f"{prefix}: out[{key!r}] on {t.device}, {source} on {device}")
+    tB, tH, tW, bs, rs = plane_view(t, f"out[{key!r}]", prefix)
+    if (tB, tH, tW) != (B, H, W):
+        raise TypeError(f"{prefix}: out[{key!r}] of shape {tuple(t.shape)} does not match {source}'s "
+                        f"{B} x {H} x {W}")
+    return t, bs, rs

@@ -1,0 +1,527 @@
+// capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
+// and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion and augment.
+// Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
+// and calls its launcher (capi_common.h).
+#include "capi_common.h"
+
+using namespace nconv::capi;
+
+extern "C" {
+
+size_t nconv_depth_loss_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 30)) return 0;
+    return nconv::loss_workspace_bytes(B, H, W);
+}
+
+// The planes of nconv_depth_loss_fwd / _bwd checked and turned into the kernels' arguments.
+static const char* loss_args(const float* r, long long rbs, long long rrs, const float* t, long long tbs,
+                             long long trs, int B, int H, int W, size_t ws_bytes, const void* ws, nconv::LossArgs& a) {
+    if (!r || !t) return "null plane";
+    if (B <= 0 || H <= 0 || W <= 0) return "non-positive B/H/W";
+    if ((long long)B * H * W > (1LL << 30)) return "batch too large";
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(r, B, H, W, 4, rbs, rrs, kNoStrideLimit, 16, kViewHW, a.r)) return why;
+    if (const char* why = view_args(t, B, H, W, 4, tbs, trs, kNoStrideLimit, 16, kViewHW, a.t)) return why;
+    if (!ws || ws_bytes < nconv::loss_workspace_bytes(B, H, W)) return "workspace too small";
+    return nullptr;
+}
+
+int nconv_depth_loss_fwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
+                         long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
+                         float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_depth_loss_fwd";
+    nconv::LossArgs a;
+    if (const char* why = loss_args(r, r_image_stride, r_row_stride, t, t_image_stride, t_row_stride, B, H, W,
+                                    workspace_bytes, workspace, a))
+        return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    return launched(fn, nconv::launch_loss_fwd, a, use_gradient_loss != 0, loss, (float*)workspace,
+                    (hipStream_t)stream);
+}
+
+int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
+                         long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
+                         const float* gloss, const void* workspace, size_t workspace_bytes, float* g, void* stream) {
+    const char* fn = "nconv_depth_loss_bwd";
+    nconv::LossArgs a;
+    if (const char* why = loss_args(r, r_image_stride, r_row_stride, t, t_image_stride, t_row_stride, B, H, W,
+                                    workspace_bytes, workspace, a))
+        return fail(-22, fn, why);
+    if (!g) return fail(-22, fn, "null g");
+    return launched(fn, nconv::launch_loss_bwd, a, use_gradient_loss != 0, gloss, (const float*)workspace, g,
+                    (hipStream_t)stream);
+}
+
+size_t nconv_depth_metrics_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 30)) return 0;
+    return nconv::metrics_workspace_bytes(B, H, W);
+}
+
+int nconv_depth_metrics(const float* pred, long long p_image_stride, long long p_row_stride, const float* gt,
+                        long long g_image_stride, long long g_row_stride, int B, int H, int W, float gt_min,
+                        float gt_max, float clamp_lo, float clamp_hi, double* sums, double* accum, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_depth_metrics";
+    if (!pred || !gt) return fail(-22, fn, "null plane");
+    if (!sums && !accum) return fail(-22, fn, "null sums and accum");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
+    nconv::MetricsArgs a;
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(pred, B, H, W, 4, p_image_stride, p_row_stride, 1LL << 31, 16, kViewHW, a.p))
+        return fail(-22, fn, why);
+    if (const char* why = view_args(gt, B, H, W, 4, g_image_stride, g_row_stride, 1LL << 31, 16, kViewHW, a.g))
+        return fail(-22, fn, why);
+    if (!(gt_min >= 0.f) || !(gt_max >= 0.f) || !(clamp_lo >= 0.f) || !(clamp_hi >= 0.f))
+        return fail(-22, fn, "negative or NaN bound");
+    if (gt_min > 0.f && gt_max > 0.f && gt_min > gt_max) return fail(-22, fn, "gt_min > gt_max");
+    if (clamp_lo > 0.f && clamp_hi > 0.f && clamp_lo > clamp_hi) return fail(-22, fn, "clamp_lo > clamp_hi");
+    if (!workspace || workspace_bytes < nconv::metrics_workspace_bytes(B, H, W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8 || (size_t)sums % 8 || (size_t)accum % 8)
+        return fail(-22, fn, "workspace / sums / accum not 8-byte aligned");
+    const float inf = __builtin_inff();
+    a.g_lo = gt_min, a.g_hi = gt_max > 0.f ? gt_max : inf;
+    a.c_lo = clamp_lo > 0.f ? clamp_lo : -inf, a.c_hi = clamp_hi > 0.f ? clamp_hi : inf;
+    return launched(fn, nconv::launch_metrics, a, sums, accum, workspace, (hipStream_t)stream);
+}
+
+int nconv_frame_ingest(const struct nconv_frame_ingest* d, void* stream) {
+    const char* fn = "nconv_frame_ingest";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->rgb && !d->plane[0].src && !d->plane[1].src) return fail(-22, fn, "nothing to do: no rgb and no planes");
+    if (d->B <= 0 || d->h <= 0 || d->w <= 0) return fail(-22, fn, "non-positive B/h/w");
+    if ((long long)d->B * d->h * d->w > (1LL << 30)) return fail(-22, fn, "batch too large");
+    const int B = d->B, h = d->h, w = d->w;
+    // views in bytes (rows of row_bytes one-byte elements), extents below 2^30 bytes
+    auto view = [&](const void* base, long long bs, long long rs, long long row_bytes, long long align,
+                    nconv::PlaneView& v) {
+        return view_args(base, B, h, row_bytes, 1, bs, rs, 1LL << 30, align, kViewBytes, v);
+    };
+    nconv::IngestArgs a{};
+    a.B = B, a.h = h, a.w = w, a.reverse = d->reverse != 0;
+    if (d->rgb) {
+        if (const char* why = view(d->rgb, d->rgb_image_stride, d->rgb_row_stride, 3LL * w, 4, a.rgb))
+            return fail(-22, fn, why);
+        if (!d->rgb_out) return fail(-22, fn, "null rgb_out");
+        if ((size_t)d->rgb_out % 4) return fail(-22, fn, "rgb_out not 4-byte aligned");
+        a.rgb_out = d->rgb_out;
+    }
+    for (int k = 0; k < 2; ++k) {
+        const nconv_frame_plane& p = d->plane[k];
+        if (!p.src) continue;
+        if (p.dtype != NCONV_FRAME_U8 && p.dtype != NCONV_FRAME_U16 && p.dtype != NCONV_FRAME_F32)
+            return fail(-22, fn, "unknown dtype (enum nconv_frame_dtype)");
+        const long long E = p.dtype == NCONV_FRAME_U8 ? 1 : p.dtype == NCONV_FRAME_U16 ? 2 : 4;
+        if (p.shift < 0 || p.shift > 15) return fail(-22, fn, "shift outside 0..15");
+        if (p.dtype == NCONV_FRAME_F32 && p.shift != 0) return fail(-22, fn, "non-zero shift with F32");
+        nconv::IngestPlane& q = a.pl[k];
+        const long long A = p.dtype == NCONV_FRAME_F32 ? 16 : 4;
+        if (const char* why = view(p.src, p.image_stride, p.row_stride, E * w, A, q.src)) return fail(-22, fn, why);
+        if ((size_t)p.src % E || q.src.rs % E || q.src.bs % E)
+            return fail(-22, fn, "U16 / F32 plane not aligned to its element size");
+        if (!p.out) return fail(-22, fn, "null plane out");
+        if ((size_t)p.out % 4) return fail(-22, fn, "plane out not 4-byte aligned");
+        q.out = p.out, q.dtype = p.dtype, q.shift = p.shift, q.scale = p.scale;
+    }
+    return launched(fn, nconv::launch_frame_ingest, a, (hipStream_t)stream);
+}
+
+int nconv_depth_export_u16(const float* pred, long long image_stride, long long row_stride, int B, int H, int W,
+                           float scale, unsigned short* out, void* stream) {
+    const char* fn = "nconv_depth_export_u16";
+    if (!pred || !out) return fail(-22, fn, "null pred or out");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)B * H * W > (1LL << 30)) return fail(-22, fn, "batch too large");
+    nconv::ExportArgs a;
+    a.B = B, a.H = H, a.W = W, a.scale = scale, a.out = out;
+    if (const char* why = view_args(pred, B, H, W, 4, image_stride, row_stride, 1LL << 31, 16, kViewHW, a.d))
+        return fail(-22, fn, why);
+    if (!(scale > 0.f) || scale == __builtin_inff()) return fail(-22, fn, "scale must be positive and finite");
+    if ((size_t)pred % 4 || (size_t)out % 2) return fail(-22, fn, "pred not 4-byte or out not 2-byte aligned");
+    return launched(fn, nconv::launch_depth_export, a, (hipStream_t)stream);
+}
+
+// The descriptor of nconv_backproject_map / _points checked and turned into the kernels' arguments
+// (with_color: the colour view is needed); NULL, or the reason it is invalid.
+static const char* backproject_args(const nconv_backproject* d, bool with_color, nconv::BackprojectArgs& a) {
+    if (!d) return "null descriptor";
+    if (!d->depth || !d->k) return "null depth or k";
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return "non-positive B/H/W";
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return "batch too large: B * H * W must be below 2^31";
+    if (nconv::backproject_segments(B, H, W) > (1LL << 24)) return "batch too large: more than 2^24 segments";
+    if (d->k_image_stride < 0) return "negative k image stride";
+    // z_max = 0 beside a z_min >= 0 would select nothing: that pair is the absent upper bound
+    const float z_max = d->z_max == 0.f && d->z_min >= 0.f ? __FLT_MAX__ : d->z_max;
+    if (!(z_max >= d->z_min)) return "z_max < z_min (or NaN)";
+    if (d->conf_min != d->conf_min) return "conf_min is NaN";
+    // fp32 planes of W elements (128-bit loads), or interleaved bytes (96-bit loads, 4-byte alignment)
+    auto view = [&](const void* base, long long bs, long long rs, bool f32, nconv::PlaneView& v) {
+        return f32 ? view_args(base, B, H, W, 4, bs, rs, 1LL << 31, 16, kViewPoints, v)
+                   : view_args(base, B, H, 3LL * W, 1, bs, rs, 1LL << 31, 4, kViewPoints, v);
+    };
+    a = nconv::BackprojectArgs{};
+    a.B = B, a.H = H, a.W = W, a.nseg = (int)nconv::backproject_segments(B, H, W);
+    if (const char* why = view(d->depth, d->depth_image_stride, d->depth_row_stride, true, a.depth)) return why;
+    if ((size_t)d->depth % 4 || (size_t)d->k % 4) return "depth or k not 4-byte aligned";
+    if (d->conf) {
+        if (const char* why = view(d->conf, d->conf_image_stride, d->conf_row_stride, true, a.conf)) return why;
+        if ((size_t)d->conf % 4) return "conf not 4-byte aligned";
+    }
+    if (d->color_kind != NCONV_COLOR_NONE && d->color_kind != NCONV_COLOR_F32_PLANAR &&
+        d->color_kind != NCONV_COLOR_U8_INTERLEAVED)
+        return "unknown color kind (enum nconv_color_kind)";
+    if ((d->color != nullptr) != (d->color_kind != NCONV_COLOR_NONE)) return "color and color_kind: both or neither";
+    if (with_color) {
+        if (!d->color) return "rgb output without a color source";
+        a.color_kind = d->color_kind, a.reverse = d->reverse != 0;
+        const bool planar = d->color_kind == NCONV_COLOR_F32_PLANAR;
+        if (const char* why = view(d->color, d->color_image_stride, d->color_row_stride, planar, a.color)) return why;
+        if (planar) {
+            if (d->color_channel_stride < H * d->color_row_stride) return "channel stride smaller than H * row stride";
+            if (B > 1 && d->color_image_stride < 2 * d->color_channel_stride + H * d->color_row_stride)
+                return "image stride smaller than H * row stride";
+            if ((size_t)d->color % 4) return "color not 4-byte aligned";
+            a.ocs = d->color_channel_stride;
+            a.color.wide = a.color.wide && a.ocs % 4 == 0;
+        }
+    }
+    a.k = d->k, a.kbs = d->k_image_stride;
+    a.z_min = d->z_min, a.z_max = z_max, a.conf_min = d->conf_min;
+    return nullptr;
+}
+
+int nconv_backproject_map(const nconv_backproject* d, float* xyz, void* stream) {
+    const char* fn = "nconv_backproject_map";
+    nconv::BackprojectArgs a;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (!xyz) return fail(-22, fn, "null xyz");
+    if ((size_t)xyz % 4) return fail(-22, fn, "xyz not 4-byte aligned");
+    return launched(fn, nconv::launch_backproject_map, a, xyz, (hipStream_t)stream);
+}
+
+size_t nconv_backproject_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    if (nconv::backproject_segments(B, H, W) > (1LL << 24)) return 0;
+    return nconv::backproject_workspace_bytes(B, H, W);
+}
+
+int nconv_backproject_points(const nconv_backproject* d, float* xyz, unsigned char* rgb, int* index,
+                             long long capacity, int* offsets, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    const char* fn = "nconv_backproject_points";
+    nconv::BackprojectArgs a;
+    if (const char* why = backproject_args(d, rgb != nullptr, a)) return fail(-22, fn, why);
+    if (capacity < 0) return fail(-22, fn, "negative capacity");
+    if (!xyz && capacity > 0) return fail(-22, fn, "null xyz");
+    if (!offsets) return fail(-22, fn, "null offsets");
+    if ((size_t)xyz % 4 || (size_t)index % 4 || (size_t)offsets % 4)
+        return fail(-22, fn, "xyz / index / offsets not 4-byte aligned");
+    if (!workspace || workspace_bytes < nconv::backproject_workspace_bytes(a.B, a.H, a.W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 4) return fail(-22, fn, "workspace not 4-byte aligned");
+    // every rank is below B * H * W < 2^31
+    const int cap = (int)(capacity < 0x7fffffffLL ? capacity : 0x7fffffffLL);
+    return launched(fn, nconv::launch_backproject_points, a, xyz, rgb, index, cap, offsets, (int*)workspace,
+                    (hipStream_t)stream);
+}
+
+// nconv_normals_opts checked and turned into the kernels' arguments (NULL: all zero)
+static const char* normals_args(const nconv_normals_opts* o, nconv::NormalsArgs& n) {
+    n = nconv::NormalsArgs{};
+    if (!o) return nullptr;
+    if (!(o->jump_rel >= 0.f) || !(o->jump_abs >= 0.f)) return "jump_rel and jump_abs must be >= 0 (and not NaN)";
+    n.jump_rel = o->jump_rel, n.jump_abs = o->jump_abs;
+    n.gate = o->jump_rel != 0.f || o->jump_abs != 0.f;
+    n.empty = (unsigned)o->empty_rgb[0] | ((unsigned)o->empty_rgb[1] << 8) | ((unsigned)o->empty_rgb[2] << 16);
+    return nullptr;
+}
+
+int nconv_depth_normals(const nconv_backproject* d, const nconv_normals_opts* o, float* normals,
+                        unsigned char* image, void* stream) {
+    const char* fn = "nconv_depth_normals";
+    nconv::BackprojectArgs a;
+    nconv::NormalsArgs n;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (const char* why = normals_args(o, n)) return fail(-22, fn, why);
+    if (!normals && !image) return fail(-22, fn, "null normals and image: nothing to write");
+    if ((size_t)normals % 4) return fail(-22, fn, "normals not 4-byte aligned");
+    return launched(fn, nconv::launch_depth_normals, a, n, normals, image, (hipStream_t)stream);
+}
+
+int nconv_depth_normals_points(const nconv_backproject* d, const nconv_normals_opts* o, const int* index,
+                               const int* offsets, long long capacity, float* normals, void* stream) {
+    const char* fn = "nconv_depth_normals_points";
+    nconv::BackprojectArgs a;
+    nconv::NormalsArgs n;
+    if (const char* why = backproject_args(d, false, a)) return fail(-22, fn, why);
+    if (const char* why = normals_args(o, n)) return fail(-22, fn, why);
+    if (capacity < 0) return fail(-22, fn, "negative capacity");
+    if (capacity > 0 && (!index || !offsets || !normals)) return fail(-22, fn, "null index, offsets or normals");
+    if ((size_t)index % 4 || (size_t)offsets % 4 || (size_t)normals % 4)
+        return fail(-22, fn, "index / offsets / normals not 4-byte aligned");
+    if (capacity == 0) return 0;
+    // every row is below B * H * W < 2^31
+    const int cap = (int)(capacity < 0x7fffffffLL ? capacity : 0x7fffffffLL);
+    return launched(fn, nconv::launch_depth_normals_points, a, n, index, offsets, cap, normals, (hipStream_t)stream);
+}
+
+size_t nconv_lidar_project_workspace_bytes(int B, int H, int W, int with_index) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return with_index ? (size_t)8 * B * H * W : 0;
+}
+
+int nconv_lidar_project(const struct nconv_lidar_project* d, float* depth, int* index, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_lidar_project";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)d->B * d->H * d->W >= (1LL << 31))
+        return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->n_rows < 0 || d->n_rows >= (1LL << 31)) return fail(-22, fn, "n_rows must be in [0, 2^31)");
+    if (d->point_stride < 3 || d->point_stride > (1 << 20))
+        return fail(-22, fn, "point_stride must be in [3, 2^20]");
+    if (!d->points && d->n_rows > 0) return fail(-22, fn, "null points");
+    if (!d->offsets || !d->m) return fail(-22, fn, "null offsets or m");
+    if (!depth) return fail(-22, fn, "null depth");
+    if (d->m_image_stride < 0) return fail(-22, fn, "negative m image stride");
+    if (!(d->z_min >= 0.f)) return fail(-22, fn, "z_min must be >= 0 (and not NaN)");
+    const float z_max = d->z_max == 0.f ? __FLT_MAX__ : d->z_max;
+    if (!(z_max >= d->z_min)) return fail(-22, fn, "z_max < z_min (or NaN)");
+    if ((size_t)d->points % 4 || (size_t)d->offsets % 4 || (size_t)d->m % 4 || (size_t)depth % 4 || (size_t)index % 4)
+        return fail(-22, fn, "points / offsets / m / depth / index not 4-byte aligned");
+    if (index) {
+        if (!workspace || workspace_bytes < nconv_lidar_project_workspace_bytes(d->B, d->H, d->W, 1))
+            return fail(-22, fn, "workspace too small");
+        if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    }
+    nconv::LidarArgs a{};
+    a.B = d->B, a.H = d->H, a.W = d->W;
+    a.n_rows = (int)d->n_rows, a.stride = d->point_stride;
+    a.vec = d->point_stride == 4 && (size_t)d->points % 16 == 0;
+    a.points = d->points, a.offsets = d->offsets, a.m = d->m, a.mbs = d->m_image_stride;
+    a.z_min = d->z_min, a.z_max = z_max;
+    return launched(fn, nconv::launch_lidar_project, a, depth, index, index ? (unsigned long long*)workspace : nullptr,
+                    (hipStream_t)stream);
+}
+
+size_t nconv_depth_colorize_workspace_bytes(int B) { return B > 0 ? (size_t)8 * B : 0; }
+
+int nconv_depth_colorize(const struct nconv_depth_colorize* d, unsigned char* out, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_depth_colorize";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->depth || !out) return fail(-22, fn, "null depth or out");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)d->B * d->H * d->W >= (1LL << 31))
+        return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->radius < 0 || d->radius > 4) return fail(-22, fn, "radius must be in [0, 4]");
+    if (!d->lut && (d->cmap_id < 0 || d->cmap_id > 4))
+        return fail(-22, fn, "cmap_id must be in [0, 4] (or give a lut)");
+    if (!d->auto_range && (d->vmin != d->vmin || d->vmax != d->vmax)) return fail(-22, fn, "vmin or vmax is NaN");
+    if (d->floor != d->floor) return fail(-22, fn, "floor is NaN");
+    if (d->auto_range) {
+        if (!workspace || workspace_bytes < nconv_depth_colorize_workspace_bytes(d->B))
+            return fail(-22, fn, "workspace too small");
+        if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    }
+    if ((size_t)d->depth % 4) return fail(-22, fn, "depth not 4-byte aligned");
+    nconv::ColorizeArgs a{};
+    a.B = d->B, a.H = d->H, a.W = d->W;
+    if (const char* why = view_args(d->depth, a.B, a.H, a.W, 4, d->image_stride, d->row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.d))
+        return fail(-22, fn, why);
+    if (d->background) {
+        if (const char* why = view_args(d->background, a.B, a.H, 3LL * a.W, 1, d->background_image_stride,
+                                        d->background_row_stride, kNoStrideLimit, 4, kViewBytes, a.bg))
+            return fail(-22, fn, (std::string("background: ") + why).c_str());
+    }
+    a.lut = d->lut, a.cmap = d->cmap_id, a.auto_range = d->auto_range != 0;
+    a.radius = d->radius, a.bgr = d->bgr != 0;
+    a.lo = d->vmin, a.hi = d->vmax, a.floor = d->floor;
+    const unsigned e0 = d->empty_rgb[a.bgr ? 2 : 0], e1 = d->empty_rgb[1], e2 = d->empty_rgb[a.bgr ? 0 : 2];
+    a.empty = e0 | (e1 << 8) | (e2 << 16);
+    a.out = out, a.range = a.auto_range ? (unsigned*)workspace : nullptr;
+    return launched(fn, nconv::launch_depth_colorize, a, (hipStream_t)stream);
+}
+
+size_t nconv_depth_sparsify_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::sparsify_workspace_bytes(B);
+}
+
+int nconv_depth_sparsify(const struct nconv_depth_sparsify* d, float* dst, long long dst_image_stride,
+                         long long dst_row_stride, int* kept, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    const char* fn = "nconv_depth_sparsify";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !dst) return fail(-22, fn, "null src or dst");
+    if (!d->state) return fail(-22, fn, "null state");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->mode < NCONV_SPARSIFY_ALL || d->mode > NCONV_SPARSIFY_FRACTION)
+        return fail(-22, fn, "unknown mode (enum nconv_sparsify_mode)");
+    if (d->mode == NCONV_SPARSIFY_COUNT_DEV && !d->n_dev) return fail(-22, fn, "COUNT_DEV without n_dev");
+    if (d->n < 0) return fail(-22, fn, "negative n");
+    if (!(d->keep >= 0.f && d->keep <= 1.f))
+        return fail(-22, fn, "keep must be in [0, 1] (and not NaN)");
+    std::string text;
+    auto view = [&](const char* name, long long bs, long long rs, bool zero_bs) {
+        // B == 1: the image stride is not read, and a negative one has always passed here
+        return flat_view(name, B, H, W, B == 1 && bs < 0 ? 0 : bs, 0, rs, 1, zero_bs, text);
+    };
+    if (const char* why = view("src", d->src_image_stride, d->src_row_stride, false)) return fail(-22, fn, why);
+    if (const char* why = view("dst", dst_image_stride, dst_row_stride, false)) return fail(-22, fn, why);
+    if (d->mask)
+        if (const char* why = view("mask", d->mask_image_stride, d->mask_row_stride, true)) return fail(-22, fn, why);
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)d->state % 4 || (size_t)d->n_dev % 4 || (size_t)kept % 4)
+        return fail(-22, fn, "src / dst / state / n_dev / kept not 4-byte aligned");
+    if (!workspace || workspace_bytes < nconv::sparsify_workspace_bytes(B)) return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    const long long sbs = B > 1 ? d->src_image_stride : 0, dbs = B > 1 ? dst_image_stride : 0;
+    const bool same = dst == d->src && dst_row_stride == d->src_row_stride && dbs == sbs;
+    if (!same && view_extent(dst, B, H, W, dbs, 0, dst_row_stride, 1, 4, "dst")
+                     .overlaps(view_extent(d->src, B, H, W, sbs, 0, d->src_row_stride, 1, 4, "src")))
+        return fail(-22, fn, "dst overlaps src without being src (same pointer and strides)");
+    nconv::SparsifyArgs a{};
+    a.B = B, a.H = H, a.W = W, a.mode = d->mode;
+    a.src = d->src, a.sbs = sbs, a.srs = d->src_row_stride;
+    a.mask = d->mask, a.mbs = B > 1 ? d->mask_image_stride : 0, a.mrs = d->mask_row_stride;
+    a.state = d->state, a.n_dev = d->n_dev, a.n = d->n, a.keep = d->keep;
+    a.all_pixels = d->all_pixels != 0, a.floor = d->floor;
+    a.key_mask = d->key_mask, a.noise_threshold = d->noise_threshold, a.noise_amp = d->noise_amp;
+    a.dst = dst, a.dbs = dbs, a.drs = dst_row_stride, a.kept = kept;
+    return launched(fn, nconv::launch_depth_sparsify, a, workspace, (hipStream_t)stream);
+}
+
+int nconv_depth_occlusion(const struct nconv_depth_occlusion* d, float* dst, long long dst_image_stride,
+                          long long dst_row_stride, unsigned char* removed, int* index, int* counts,
+                          void* stream) {
+    const char* fn = "nconv_depth_occlusion";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !dst) return fail(-22, fn, "null src or dst");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->rh < 0 || d->rh > 16 || d->rw < 0 || d->rw > 16) return fail(-22, fn, "rh and rw must be in [0, 16]");
+    if (!(d->jump_abs >= 0.f) || !(d->jump_rel >= 0.f)) return fail(-22, fn, "jump_abs or jump_rel is negative or NaN");
+    if (d->floor != d->floor) return fail(-22, fn, "floor is NaN");
+    if (d->min_support < 1) return fail(-22, fn, "min_support must be at least 1");
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)index % 4 || (size_t)counts % 4)
+        return fail(-22, fn, "src / dst / index / counts not 4-byte aligned");
+    nconv::OcclusionArgs a{};
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(d->src, B, H, W, 4, d->src_image_stride, d->src_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.s))
+        return fail(-22, fn, (std::string("src: ") + why).c_str());
+    nconv::PlaneView dv{};
+    if (const char* why = view_args(dst, B, H, W, 4, dst_image_stride, dst_row_stride, kNoStrideLimit, 16, kViewPoints, dv))
+        return fail(-22, fn, (std::string("dst: ") + why).c_str());
+    // neighbours are read: the byte extents of the two views must be disjoint
+    if (view_extent(dst, B, H, W, dv.bs, 0, dv.rs, 1, 4, "dst")
+            .overlaps(view_extent(d->src, B, H, W, a.s.bs, 0, a.s.rs, 1, 4, "src")))
+        return fail(-22, fn, "dst overlaps src (no in-place operation: neighbours are read)");
+    a.rh = d->rh, a.rw = d->rw, a.min_support = d->min_support;
+    a.jump_abs = d->jump_abs, a.jump_rel = d->jump_rel, a.floor = d->floor;
+    a.dst = dst, a.dbs = dv.bs, a.drs = dv.rs;
+    a.removed = removed, a.index = index, a.counts = counts;
+    return launched(fn, nconv::launch_depth_occlusion, a, (hipStream_t)stream);
+}
+
+int nconv_frame_augment(const struct nconv_frame_augment* d, void* stream) {
+    using namespace nconv;
+    const char* fn = "nconv_frame_augment";
+    auto bad = [&](const char* why) { return fail(-22, fn, why); };
+    auto bad_amp = [](float v) { return !(v >= 0.f && v <= 1.f); };
+    if (!d) return bad("null descriptor");
+    if (!d->state) return bad("null state");
+    bool any = d->rgb || d->mask || d->k;
+    for (int i = 0; i < 3; ++i) any = any || d->plane[i].src;
+    if (!any) return bad("no source at all (rgb, plane, mask or k)");
+    if (!d->rgb != !d->rgb_out) return bad("rgb and rgb_out go together: one of them is null");
+    for (int i = 0; i < 3; ++i)
+        if (!d->plane[i].src != !d->plane[i].out) return bad("a plane's src and out go together: one of them is null");
+    if (!d->mask != !d->mask_out) return bad("mask and mask_out go together: one of them is null");
+    if (!d->k != !d->k_out) return bad("k and k_out go together: one of them is null");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->h <= 0 || d->w <= 0) return bad("non-positive B/H/W/h/w");
+    const int B = d->B, H = d->H, W = d->W, h = d->h, w = d->w;
+    if (h > H || w > W) return bad("the output size (h, w) exceeds the source size (H, W)");
+    if ((long long)B * 3 * H * W >= (1LL << 31)) return bad("batch too large: B * 3 * H * W must be below 2^31");
+    for (int m : {d->mode_y, d->mode_x})
+        if (m < NCONV_AUGMENT_RANDOM || m > NCONV_AUGMENT_MAX) return bad("unknown mode (enum nconv_augment_crop)");
+    if (d->flip_threshold > (1ULL << 32)) return bad("flip_threshold above 2^32");
+    if (bad_amp(d->brightness) || bad_amp(d->contrast) || bad_amp(d->color))
+        return bad("brightness, contrast and color must be in [0, 1] (and not NaN)");
+    if (d->pivot != d->pivot || !(d->rgb_max >= 0.f)) return bad("pivot is NaN, or rgb_max is NaN or negative");
+
+    // the views: strides, and the byte extents of every source and output
+    std::string text;
+    // sources: state, rgb, three planes, mask, k; outputs: rgb, three planes, mask, k, params, gains
+    Extent srcs[7], outs[8];
+    int ns = 0, no = 0;
+    srcs[ns++] = flat_extent(d->state, 12, "state");
+    if ((size_t)d->state % 4) return bad("state not 4-byte aligned");
+    if (d->rgb) {
+        const long long bs = d->rgb_image_stride, cs = d->rgb_channel_stride, rs = d->rgb_row_stride;
+        if (const char* why = flat_view("rgb", B, H, W, bs, cs, rs, 3, false, text)) return bad(why);
+        if ((size_t)d->rgb % 4 || (size_t)d->rgb_out % 4) return bad("rgb / rgb_out not 4-byte aligned");
+        srcs[ns++] = view_extent(d->rgb, B, H, W, bs, cs, rs, 3, 4, "rgb");
+        outs[no++] = flat_extent(d->rgb_out, 12LL * B * h * w, "rgb_out");
+    }
+    static const char* const plane_names[3] = {"plane[0]", "plane[1]", "plane[2]"};
+    for (int i = 0; i < 3; ++i) {
+        const nconv_augment_plane& pl = d->plane[i];
+        if (!pl.src) continue;
+        if (const char* why = flat_view(plane_names[i], B, H, W, pl.image_stride, 0, pl.row_stride, 1, false, text))
+            return bad(why);
+        if ((size_t)pl.src % 4 || (size_t)pl.out % 4) return bad("a plane's src / out not 4-byte aligned");
+        srcs[ns++] = view_extent(pl.src, B, H, W, pl.image_stride, 0, pl.row_stride, 1, 4, plane_names[i]);
+        outs[no++] = flat_extent(pl.out, 4LL * B * h * w, plane_names[i]);
+    }
+    if (d->mask) {
+        if (const char* why = flat_view("mask", B, H, W, d->mask_image_stride, 0, d->mask_row_stride, 1, true, text))
+            return bad(why);
+        srcs[ns++] = view_extent(d->mask, B, H, W, d->mask_image_stride, 0, d->mask_row_stride, 1, 1, "mask");
+        outs[no++] = flat_extent(d->mask_out, 1LL * B * h * w, "mask_out");
+    }
+    if (d->k) {
+        if ((size_t)d->k % 4 || (size_t)d->k_out % 4) return bad("k / k_out not 4-byte aligned");
+        srcs[ns++] = flat_extent(d->k, 36LL * B, "k");
+        outs[no++] = flat_extent(d->k_out, 36LL * B, "k_out");
+    }
+    if ((size_t)d->params % 4 || (size_t)d->gains % 4) return bad("params / gains not 4-byte aligned");
+    if (d->params) outs[no++] = flat_extent(d->params, 16LL * B, "params");
+    if (d->gains) outs[no++] = flat_extent(d->gains, 20LL * B, "gains");
+    for (int i = 0; i < no; ++i)
+        for (int j = 0; j < ns; ++j)
+            if (outs[i].overlaps(srcs[j])) {
+                text = std::string("output ") + outs[i].name + " overlaps source " + srcs[j].name;
+                return bad(text.c_str());
+            }
+
+    AugmentArgs a{};
+    a.B = B, a.H = H, a.W = W, a.h = h, a.w = w;
+    a.mode_y = d->mode_y, a.mode_x = d->mode_x, a.flip_threshold = d->flip_threshold;
+    a.brightness = d->brightness, a.contrast = d->contrast, a.color = d->color;
+    a.pivot = d->pivot, a.rgb_max = d->rgb_max;
+    a.jitter = !(d->brightness == 0.f && d->contrast == 0.f && d->color == 0.f);
+    a.state = d->state;
+    const long long hw = (long long)h * w;
+    if (d->rgb)
+        for (int c = 0; c < 3; ++c)
+            a.slot[a.nslots++] = AugmentSlot{d->rgb + c * d->rgb_channel_stride, d->rgb_out + c * hw,
+                                             B > 1 ? d->rgb_image_stride : 0, d->rgb_row_stride, 3 * hw, kRgb, c};
+    for (int i = 0; i < 3; ++i)
+        if (d->plane[i].src)
+            a.slot[a.nslots++] = AugmentSlot{d->plane[i].src, d->plane[i].out, B > 1 ? d->plane[i].image_stride : 0,
+                                             d->plane[i].row_stride, hw, kPlane, 0};
+    if (d->mask)
+        a.slot[a.nslots++] = AugmentSlot{d->mask, d->mask_out, B > 1 ? d->mask_image_stride : 0, d->mask_row_stride,
+                                         hw, kMask, 0};
+    a.k = d->k, a.k_out = d->k_out, a.params = d->params, a.gains = d->gains;
+    return launched(fn, launch_frame_augment, a, (hipStream_t)stream);
+}
+
+}  // extern "C"

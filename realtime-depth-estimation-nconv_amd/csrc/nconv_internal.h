@@ -1,5 +1,5 @@
-// nconv_internal.h — launcher interface between the C-ABI layer (nconv_capi.hip) and the kernel
-// translation units. Not part of the public ABI.
+// nconv_internal.h — launcher interface between the C-ABI layer (nconv_capi.hip, capi_dense.hip,
+// capi_io.hip) and the kernel translation units. Not part of the public ABI.
 #pragma once
 #include "nconv_common.h"
 
@@ -216,7 +216,7 @@ int launch_bn_train_bwd(const nconv_bn_train& p, const float* gy, float* gx, flo
                         hipStream_t st, const char** why);
 
 // A batch of B planes of H rows as the I/O kernels read it (plane_io.h); checked and filled by
-// view_args in nconv_capi.hip. Strides are in the unit the owning struct states.
+// view_args in capi_common.h. Strides are in the unit the owning struct states.
 struct PlaneView {
     const void* base;
     long long bs;  // image stride; 0 where B == 1
@@ -380,8 +380,30 @@ struct OcclusionArgs {
 };
 int launch_depth_occlusion(const OcclusionArgs& a, hipStream_t st, const char** why);
 
-// Records "<fn>: <why>" as the calling thread's nconv_last_error() text and returns code: for an entry
-// point that lives beside its kernel (nconv_frame_augment, augment.hip). Defined in nconv_capi.hip.
-int capi_fail(int code, const char* fn, const char* why);
+// Random crop, flip and colour jitter of a training batch (nconv_frame_augment), augment.hip.
+enum SlotKind { kPlane = 0, kRgb = 1, kMask = 2 };
+struct AugmentSlot {
+    const void* src;   // image 0 (of this channel)
+    void* dst;
+    long long bs, rs;  // source strides: elements (bytes for the mask); bs 0 where B == 1
+    long long dbs;     // output image stride in elements
+    int kind, chan;
+};
+constexpr int kMaxSlots = 7;  // three RGB channels, three planes, the mask
+struct AugmentArgs {
+    int B, H, W, h, w;
+    int mode_y, mode_x;
+    unsigned long long flip_threshold;
+    float brightness, contrast, color, pivot, rgb_max;
+    int jitter;
+    const unsigned* state;
+    int nslots;
+    AugmentSlot slot[kMaxSlots];
+    const float* k;
+    float* k_out;
+    int* params;
+    float* gains;
+};
+int launch_frame_augment(const AugmentArgs& a, hipStream_t st, const char** why);
 
 }  // namespace nconv

@@ -380,7 +380,7 @@ int launch_wgrad_reduce_multi(int n, const RedJob* jobs, hipStream_t st, const c
     for (int k = n + 1; k <= kMaxRedJobs; ++k) T.x0[k] = T.f0[k] = 0;
     hipLaunchKernelGGL(wgrad_reduce_sum, dim3(T.x0[n], kReduceSplit), dim3(kT), 0, st, T);
     hipLaunchKernelGGL(wgrad_finish, dim3(T.f0[n]), dim3(kT), 0, st, T);
-    return 0;
+    return launch_status(why);
 }
 
 // part: nblk partial rows followed by kReduceSplit rows of slice sums (see bwd_layout);

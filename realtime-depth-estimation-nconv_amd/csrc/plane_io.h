@@ -2,7 +2,7 @@
 // (metrics.hip, frame_io.hip, backproject.hip; loss.hip and lidar_project.hip take the constants).
 //
 // A view is a batch of planes given as (base, image stride, row stride): PlaneView in
-// nconv_internal.h, checked and filled on the host by view_args in nconv_capi.hip. A kernel reads
+// nconv_internal.h, checked and filled on the host by view_args in capi_common.h. A kernel reads
 // image b through a buffer resource over exactly that image's extent,
 //   [base + b * image stride, + ((H - 1) * row stride + row elements) * element bytes),
 // which the host keeps below 2^31 bytes, so that the byte offset kOOB lies past every resource and a

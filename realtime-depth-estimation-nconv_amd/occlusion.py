@@ -97,16 +97,7 @@ def remove_occluded(S, window=(3, 3), jump_abs=1.0, jump_rel=0.0, min_support=1,
         _views.on_device(index, "index", _PREFIX, _DOING)
         if index.device != dev:
             raise RuntimeError(f"{_PREFIX}: index on {index.device}, S on {dev}")
-    dst = None if out is None else out.get("depth")
-    if dst is None:
-        dst = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-    else:
-        _views.require_tensor(dst, "out['depth']", (torch.float32,), _PREFIX)
-        if dst.device != dev:
-            raise RuntimeError(f"{_PREFIX}: out['depth'] on {dst.device}, S on {dev}")
-    dB, dH, dW, dbs, drs = _views.plane_view(dst, "out['depth']", _PREFIX)
-    if (dB, dH, dW) != (B, H, W):
-        raise TypeError(f"{_PREFIX}: out['depth'] of shape {tuple(dst.shape)} does not match S {tuple(S.shape)}")
+    dst, dbs, drs = _views.dest_plane(out, "depth", B, H, W, dev, _PREFIX, source="S")
     removed = counts = None
     if return_removed:
         removed = _views.output(out, "removed", (B, H, W), torch.uint8, dev, _PREFIX, source="S")

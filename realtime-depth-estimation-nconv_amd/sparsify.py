@@ -130,17 +130,7 @@ def sparsify(depth, n=None, *, keep=None, seed=0, draw=0, state=None, mask=None,
             _on_device(t, what)
             if t.device != dev:
                 raise RuntimeError(f"{_PREFIX}: {what} on {t.device}, depth on {dev}")
-    dst = None if out is None else out.get("depth")
-    if dst is None:
-        dst = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-    else:
-        _views.require_tensor(dst, "out['depth']", (torch.float32,), _PREFIX)
-        if dst.device != dev:
-            raise RuntimeError(f"{_PREFIX}: out['depth'] on {dst.device}, the depth on {dev}")
-    dB, dH, dW, dbs, drs = _views.plane_view(dst, "out['depth']", _PREFIX)
-    if (dB, dH, dW) != (B, H, W):
-        raise TypeError(f"{_PREFIX}: out['depth'] of shape {tuple(dst.shape)} does not match depth "
-                        f"{tuple(depth.shape)}")
+    dst, dbs, drs = _views.dest_plane(out, "depth", B, H, W, dev, _PREFIX, source="the depth")
     kept = _output(out, "kept", (B,), torch.int32, dev) if (return_kept or (out and "kept" in out)) else None
     nws = workspace_bytes(B, H, W)
     ws = _output(out, "workspace", (nws,), torch.uint8, dev)

@@ -52,6 +52,21 @@ int main(void) {
     /* one row into src: neither src itself nor clear of it */
     rc = nconv_depth_sparsify(&d, (float*)(0x100000 + 640 * 4), 0, 640, NULL, ws, need, NULL);
     printf("\"rc_overlap\": [%d, \"%s\"],\n", rc, nconv_last_error());
+    /* a batch of two: image strides one element short, a short mask row, a stride above 2^40 */
+    const long long plane = 480LL * 640;
+    const size_t need2 = nconv_depth_sparsify_workspace_bytes(2, 480, 640);
+    d.B = 2; d.src_image_stride = plane;
+    rc = nconv_depth_sparsify(&d, dst, plane - 1, 640, NULL, ws, need2, NULL);
+    printf("\"rc_dst_image_stride\": [%d, \"%s\"],\n", rc, nconv_last_error());
+    d.mask = (const unsigned char*)0x4000000; d.mask_row_stride = 639;
+    rc = nconv_depth_sparsify(&d, dst, plane, 640, NULL, ws, need2, NULL);
+    printf("\"rc_mask_row_stride\": [%d, \"%s\"],\n", rc, nconv_last_error());
+    d.mask_row_stride = 640; d.mask_image_stride = plane - 1;
+    rc = nconv_depth_sparsify(&d, dst, plane, 640, NULL, ws, need2, NULL);
+    printf("\"rc_mask_image_stride\": [%d, \"%s\"],\n", rc, nconv_last_error());
+    d.mask = NULL;
+    rc = nconv_depth_sparsify(&d, dst, (1LL << 41) * 480, (1LL << 40) + 1, NULL, ws, need2, NULL);
+    printf("\"rc_stride_cap\": [%d, \"%s\"],\n", rc, nconv_last_error());
     printf("\"abi\": [%d, %d]\n}\n", nconv_abi_version(), NCONV_ABI_VERSION);
     return 0;
 }

@@ -5,17 +5,15 @@ invariants (window in range and reaching both ends, the flip share, copies, hand
 rewritten intrinsics keep every pixel's ray); the Python function refuses CPU tensors and malformed
 arguments."""
 import ctypes
-import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import augment_cases as AC
+import host_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nconv.h")
@@ -24,17 +22,7 @@ F32, U32 = np.float32, np.uint32
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "augment_host")
-    csrc = os.path.join(os.path.dirname(nconv_amd.__file__), "csrc")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                    os.path.join(ROOT, "tests", "host", "augment_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "augment_host", csrc=True)
 
 
 def _f(bits):
@@ -62,10 +50,7 @@ def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     L = nconv_amd._lib
     want = {}
     for name, S in (("nconv_frame_augment", L.NconvFrameAugment), ("nconv_augment_plane", L.NconvAugmentPlane)):
-        want[name] = [0, ctypes.sizeof(S)]
-        for f, _ in S._fields_:
-            d = getattr(S, f)
-            want[f"{name}.{f}"] = [d.offset, d.size]
+        want.update(host_harness.ctypes_layout(S, name))
     c = {k: v for k, v in host_report.items() if k.startswith(("nconv_frame_augment", "nconv_augment_plane"))}
     assert len(c) == 1 + 28 + 1 + 4 and c == want
     assert host_report["modes"] == [L.AUGMENT_CROPS[m] for m in ("random", "center", "min", "max")] == [0, 1, 2, 3]

@@ -4,41 +4,19 @@ tests/host/capi_host.c is built with gcc against the public header and linked to
 reports sizeof/offsetof of every ABI struct field, which must equal the ctypes structures of
 realtime-depth-estimation-nconv_amd/_lib.py (so header, binding and INTEGRATION.md cannot drift
 apart silently), and makes host-validated calls that must return -EINVAL with a message."""
-import ctypes
-import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+import host_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    if not os.path.exists(lib):
-        pytest.skip("libnconv.so not built")
-    exe = str(tmp_path_factory.mktemp("host") / "capi_host")
-    libdir = os.path.dirname(lib)
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "capi_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{libdir}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
-
-
-def _ctypes_layout(struct):
-    out = {struct.__name__: [0, ctypes.sizeof(struct)]}
-    for name, _ in struct._fields_:
-        f = getattr(struct, name)
-        out[f"{struct.__name__}.{name}"] = [f.offset, f.size]
-    return out
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "capi_host")
 
 
 @pytest.mark.parametrize("c_name,py_name", [("nconv_src", "NconvSrc"), ("nconv_layer", "NconvLayer"),
@@ -47,8 +25,8 @@ def _ctypes_layout(struct):
                                             ("nconv_bwd_io", "NconvBwdIo"),
                                             ("nconv_bn_train", "NconvBnTrain")])
 def test_struct_layout_matches_ctypes(nconv_amd, host_report, c_name, py_name):
-    py = _ctypes_layout(getattr(nconv_amd._lib, py_name))
-    c = {k.replace(c_name, py_name, 1): v for k, v in host_report.items() if k == c_name or k.startswith(c_name + ".")}
+    py = host_harness.ctypes_layout(getattr(nconv_amd._lib, py_name), c_name)
+    c = {k: v for k, v in host_report.items() if k == c_name or k.startswith(c_name + ".")}
     assert c == py
 
 

@@ -5,11 +5,8 @@ every malformed call fails on the host with -22 before any launch; visualize.* r
 arguments and CPU tensors; compat save_depth on a host array writes what it always wrote."""
 import ctypes
 import importlib.util
-import json
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -17,6 +14,7 @@ import pytest
 import torch
 
 import colorize_cases as CC
+import host_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nconv.h")
@@ -130,24 +128,12 @@ def test_entry_points_exported_and_declared(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "colorize_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "colorize_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "colorize_host")
 
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvDepthColorize
-    want = {"nconv_depth_colorize": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_depth_colorize.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_depth_colorize")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_depth_colorize")}
     assert len(c) == 19 and c == want
     assert host_report["desc_typedef"] == ctypes.sizeof(S)

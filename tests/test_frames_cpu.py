@@ -5,12 +5,9 @@ pushed through the numpy reference equal the raw=False samples bit for bit; the 
 round-trips; DevicePrefetcher keeps today's positional call."""
 import ctypes
 import inspect
-import json
 import os
 import random
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +15,7 @@ import torch
 from PIL import Image
 
 import frames_cases as FC
+import host_harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nconv.h")
@@ -37,31 +35,14 @@ def test_entry_points_exported_and_declared(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "frames_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "frames_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
-
-
-def _ctypes_layout(struct, name):
-    out = {name: [0, ctypes.sizeof(struct)]}
-    for f, _ in struct._fields_:
-        d = getattr(struct, f)
-        out[f"{name}.{f}"] = [d.offset, d.size]
-    return out
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "frames_host")
 
 
 @pytest.mark.parametrize("c_name,py_name", [("nconv_frame_plane", "NconvFramePlane"),
                                             ("nconv_frame_ingest_desc", "NconvFrameIngest")])
 def test_struct_layout_matches_ctypes(nconv_amd, host_report, c_name, py_name):
     c = {k: v for k, v in host_report.items() if k == c_name or k.startswith(c_name + ".")}
-    assert len(c) > 5 and c == _ctypes_layout(getattr(nconv_amd._lib, py_name), c_name)
+    assert len(c) > 5 and c == host_harness.ctypes_layout(getattr(nconv_amd._lib, py_name), c_name)
 
 
 def test_host_calls_and_enum(nconv_amd, host_report):

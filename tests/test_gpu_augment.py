@@ -4,10 +4,6 @@ each one alone; strided, misaligned and shared views; the jitter, its clamp and 
 against the C host's; KITTI size; determinism; Augmenter under torch.cuda.graph; Augment behind
 DevicePrefetcher; refusals."""
 import itertools
-import json
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +11,11 @@ import torch
 
 import augment_cases as AC
 import frames_cases as FC
+import host_harness
 import sparsify_cases as SC
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, U32 = np.float32, np.uint32
 GUARD = {torch.float32: -7.0, torch.uint8: 0x5A, torch.int32: -77}
 MODE_NAMES = ("random", "center", "min", "max")
@@ -184,16 +180,7 @@ def test_strided_misaligned_and_shared_views(nconv_amd, gpu, gi):
 @pytest.fixture(scope="module")
 def host_gains(nconv_amd, tmp_path_factory):
     """augment_params.h on the host: (seed, draw, b, amplitudes) -> the five gains' bits."""
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "augment_host")
-    csrc = os.path.join(os.path.dirname(nconv_amd.__file__), "csrc")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                    os.path.join(ROOT, "tests", "host", "augment_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    rows = json.loads(subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120).stdout)["draws"]
+    rows = host_harness.host_report(nconv_amd, tmp_path_factory, "augment_host", csrc=True)["draws"]
     return {tuple(r[:13]): r[16:] for r in rows}
 
 

@@ -4,16 +4,14 @@ kitti_projection against a hand-written product; read_velodyne_bin; the entry po
 exported, declared and bound with the C struct's layout; every malformed call fails on the host with
 -22 before any launch; lidar.* refuse malformed arguments and CPU tensors."""
 import ctypes
-import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_harness
 import lidar_cases as LC
 import pointcloud_cases as PC
 
@@ -231,24 +229,12 @@ def test_entry_points_exported_and_declared(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "lidar_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "lidar_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "lidar_host")
 
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvLidarProject
-    want = {"nconv_lidar_project": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_lidar_project.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_lidar_project")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_lidar_project")}
     assert len(c) == 12 and c == want
     assert host_report["desc_typedef"] == ctypes.sizeof(S)

@@ -4,17 +4,15 @@ declared and bound with the C struct's layout under an unchanged ABI number; eve
 fails on the host with -22 before any launch; the Python functions refuse CPU tensors and malformed
 arguments; write_ply with normals round-trips and is unchanged without them."""
 import ctypes
-import json
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_harness
 import normals_cases as NC
 import pointcloud_cases as PC
 
@@ -196,24 +194,12 @@ def test_entry_points_exported_and_abi_unchanged(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "normals_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "normals_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "normals_host")
 
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvNormalsOpts
-    want = {"nconv_normals_opts": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_normals_opts.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_normals_opts")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_normals_opts")}
     assert len(c) == 4 and c == want and want["nconv_normals_opts"] == [0, 12]
 

@@ -4,16 +4,14 @@ bound with the C struct's layout under an unchanged ABI number; every malformed 
 with -22 before any launch; the Python function refuses CPU tensors and malformed arguments; on a
 constructed wall-and-background scene every see-through return is removed."""
 import ctypes
-import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_harness
 import lidar_cases as LC
 import occlusion_cases as OC
 
@@ -105,24 +103,12 @@ def test_entry_point_exported_and_declared(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "occlusion_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "occlusion_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "occlusion_host")
 
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvDepthOcclusion
-    want = {"nconv_depth_occlusion": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_depth_occlusion.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_depth_occlusion")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_depth_occlusion")}
     assert len(c) == 13 and c == want
     assert host_report["desc_typedef"] == ctypes.sizeof(S)

@@ -4,17 +4,15 @@ exported, declared and bound with the C struct's layout; every malformed call fa
 -22 before any launch; pointcloud.* refuse CPU tensors and malformed arguments;
 DNET.forward_with_confidence refuses grad mode and CPU input."""
 import ctypes
-import json
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_harness
 import pointcloud_cases as PC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -143,24 +141,12 @@ def test_entry_points_exported_and_declared(nconv_amd):
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "pointcloud_host")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "host", "pointcloud_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "pointcloud_host")
 
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvBackproject
-    want = {"nconv_backproject": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_backproject.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_backproject")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_backproject")}
     assert len(c) == 21 and c == want
 

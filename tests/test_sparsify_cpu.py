@@ -5,18 +5,16 @@ unchanged ABI number; every malformed call fails on the host with -22 before any
 function refuses CPU tensors and malformed arguments; DataLoader_NYU(sparse="device") samples carry the
 right keys and sparse="host" is bit-identical to the reference's preprocess_depth."""
 import ctypes
-import json
 import os
 import random
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
 
+import host_harness
 import sparsify_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,17 +37,7 @@ def test_philox_known_answers_reference():
 
 @pytest.fixture(scope="module")
 def host_report(nconv_amd, tmp_path_factory):
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("gcc not available")
-    lib = nconv_amd._lib.LIB_PATH
-    exe = str(tmp_path_factory.mktemp("host") / "sparsify_host")
-    csrc = os.path.join(os.path.dirname(nconv_amd.__file__), "csrc")
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                    os.path.join(ROOT, "tests", "host", "sparsify_host.c"), "-o", exe, lib,
-                    f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=120)
-    return json.loads(r.stdout)
+    return host_harness.host_report(nconv_amd, tmp_path_factory, "sparsify_host", csrc=True)
 
 
 def test_philox_known_answers_host(host_report):
@@ -59,10 +47,7 @@ def test_philox_known_answers_host(host_report):
 
 def test_struct_layout_matches_ctypes(nconv_amd, host_report):
     S = nconv_amd._lib.NconvDepthSparsify
-    want = {"nconv_depth_sparsify": [0, ctypes.sizeof(S)]}
-    for f, _ in S._fields_:
-        d = getattr(S, f)
-        want[f"nconv_depth_sparsify.{f}"] = [d.offset, d.size]
+    want = host_harness.ctypes_layout(S, "nconv_depth_sparsify")
     c = {k: v for k, v in host_report.items() if k.startswith("nconv_depth_sparsify")}
     assert len(c) == 20 and c == want
 
@@ -72,7 +57,9 @@ def test_host_calls(host_report):
     need, none = host_report["workspace_bytes"]
     assert need == 6 * (2048 * 4 + 16) and none == 0
     for key, msg in (("rc_workspace", "workspace too small"), ("rc_row_stride", "row stride"), ("rc_state", "null state"),
-                     ("rc_mode", "unknown mode"), ("rc_overlap", "overlaps src")):
+                     ("rc_mode", "unknown mode"), ("rc_overlap", "overlaps src"),
+                     ("rc_dst_image_stride", "dst: image stride"), ("rc_mask_row_stride", "mask: row stride"),
+                     ("rc_mask_image_stride", "mask: image stride"), ("rc_stride_cap", "too large")):
         rc, err = host_report[key]
         assert rc == -22 and msg in err, (key, rc, err)
 
