@@ -32,6 +32,7 @@ get_optimizer = _m.train.get_optimizer
 save_checkpoint = _m.train.save_checkpoint
 DepthMetrics = _m.metrics.DepthMetrics
 depth_metric_sums = _m.metrics.depth_metric_sums
+SparsificationCurves = _m.SparsificationCurves
 
 
 def save_depth(depth_data, path, cmap=None):
@@ -95,6 +96,22 @@ def get_metrics(model, val_loader, device_str, unit_m=1.0, **bounds):
             depth, gt = data["depth"].to(device), data["gt"].to(device)
             metrics.update(model(depth), gt)
     return metrics.compute(unit_m)
+
+
+def get_sparsification(model, val_loader, device_str, steps=100, **bounds):
+    """Sparsification curves and AUSE (nconv_amd.SparsificationCurves.compute) of a step-1 model's output
+    confidence over every image of every batch: get_metrics's loop on model.forward_with_confidence, one
+    fused call per batch and one synchronisation at the end. bounds: gt_min, gt_max, clamp=(lo, hi)."""
+    device = torch.device(device_str if device_str == "cuda" and torch.cuda.is_available() else "cpu")
+    model.to(device)
+    model.eval()
+    curves = SparsificationCurves(steps=steps, device=device, **bounds)
+    with torch.no_grad():
+        for data in val_loader:
+            depth, gt = data["depth"].to(device), data["gt"].to(device)
+            pred, conf = model.forward_with_confidence(depth)
+            curves.update(pred, gt, conf)
+    return curves.compute()
 
 
 def get_metrics_multi_resolution(model, val_loader, device_str, unit_m=1.0, **bounds):

@@ -1081,6 +1081,73 @@ typedef struct nconv_frame_augment {
  * that overlaps a source extent (state counts as a source). */
 int nconv_frame_augment(const struct nconv_frame_augment* d, void* stream);
 
+/* Added under ABI 27 (purely additive: two new entry points and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). Sparsification curves of a confidence plane (Ilg et al. 2018):
+ * remove the least confident valid pixels step by step and sum the error of the rest, beside the oracle
+ * that removes the largest errors first. pred, gt and conf are B planes (H, W) of fp32, each with image
+ * and row strides in elements (cropped views, and a first element that is not 16-byte aligned, are
+ * allowed, as in nconv_depth_metrics). Per image b, with pixel number p = row * W + col:
+ *   valid      as in nconv_depth_metrics: gt > 0, gt >= gt_min, gt <= gt_max (a bound of 0 is absent);
+ *              n_b = the number of valid pixels.
+ *   terms      P = pred clamped into [clamp_lo, clamp_hi] by comparisons (a bound of 0 is absent; a NaN
+ *              stays NaN); e = P - gt, a = |e|, q = e * e, in fp32 with no contraction.
+ *   conf key   bits = as_uint(conf); u = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000), which preserves
+ *              the order of the floats (-0.0 ranks below +0.0). With uncertainty != 0 the plane is an
+ *              uncertainty (larger is worse) and the key is ~u. A NaN conf has the key 0 under either
+ *              reading: it is removed first.
+ *   oracle key v = ~as_uint(a): the largest error first, a NaN error before +inf.
+ *   order      for each ranking o (0: conf key, 1: oracle key) the valid pixels sorted by ascending key,
+ *              ties broken by ascending p. No two elements compare equal, so the order is unique.
+ *   curve      steps = J in [1, 1024]; for j = 0 .. J-1, k_j = floor(j * n_b / J) in 64-bit integers, the
+ *              kept set is positions k_j .. n_b - 1 of the order, and
+ *                curves[b][o][j] = { n_b - k_j, sum of a, sum of q } over the kept set (three doubles).
+ *              n_b == 0 gives rows of zeros.
+ * The count is exact. The summation order is fixed: the sorted positions are cut into chunks of 256; the
+ * terms of a chunk, as doubles, are thread values t = 0 .. 255 of a tree T that adds values t and t ^ 32,
+ * then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 inside each group of 64, then ((g0 + g1) + g2) + g3 over the four groups;
+ * absent positions count as +0.0. With c = floor(k_j / 256), thread value t for curve point j is the term at
+ * position 256 c + t where that lies in [k_j, n_b), else 0, plus the T-sums of chunks c + 1 + t,
+ * c + 1 + t + 256, .. in that order; the point is T over those 256 values. The same input gives the same
+ * bits on every run. No floating-point atomics, no global atomics.
+ * curves: (B, 2, J, 3) doubles, 8-byte aligned, overwritten. order: optional (B, 2, H * W) int32;
+ * order[b][o][0 .. n_b) holds the pixel numbers in removal order, the rest is -1; NULL skips it.
+ * The sort is a segmented (image x ranking), stable, least-significant-digit radix sort of (key, p) pairs
+ * with 8-bit digits; invalid pixels are left out by a raster-order compaction beforehand, which is also
+ * what makes p the tie-break. Twelve launches on `stream` whatever the data, n_b and order; no host
+ * synchronisation, no allocation: capturable. Every buffer lives in the workspace (8-byte aligned,
+ * about 40 bytes per pixel of the batch).
+ * -EINVAL before any launch for a NULL descriptor, plane or curves; B, H or W <= 0; steps outside
+ * [1, 1024]; H * W >= 2^31 (pixel numbers are int32) or B * H * W >= 2^31; a view whose row stride is below W,
+ * whose image stride is below H * row stride, or whose extent ((H - 1) * row stride + W) * 4 reaches 2^31
+ * bytes ("plane too large"); a negative or NaN bound, gt_min > gt_max, clamp_lo > clamp_hi; planes or order
+ * not 4-byte aligned, curves not 8-byte aligned; a workspace that is NULL, too small or not 8-byte aligned.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_sparsification`
+ * or nconv_depth_sparsification_desc) */
+#define NCONV_SPARSIFICATION_MAX_STEPS 1024
+typedef struct nconv_depth_sparsification {
+    int B, H, W;
+    int steps;                      /* J: 1 .. 1024                                                */
+    const float* pred;              /* fp32 views, 4-byte aligned                                  */
+    long long pred_image_stride;    /* elements; ignored when B == 1                               */
+    long long pred_row_stride;      /* elements, >= W                                              */
+    const float* gt;
+    long long gt_image_stride;
+    long long gt_row_stride;
+    const float* conf;
+    long long conf_image_stride;
+    long long conf_row_stride;
+    float gt_min, gt_max;           /* validity window of gt; 0: absent                            */
+    float clamp_lo, clamp_hi;       /* clamp window of pred; 0: absent                             */
+    int uncertainty;                /* != 0: conf is an uncertainty, the largest is removed first  */
+    double* curves;                 /* (B, 2, J, 3)                                                */
+    int* order;                     /* optional (B, 2, H * W)                                      */
+} nconv_depth_sparsification_desc;
+
+/* 0 for extents or steps that the call itself refuses. */
+size_t nconv_depth_sparsification_workspace_bytes(int B, int H, int W, int steps);
+int nconv_depth_sparsification(const struct nconv_depth_sparsification* d, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

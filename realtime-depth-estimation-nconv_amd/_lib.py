@@ -41,6 +41,7 @@ CMAP_IDS = {"inferno": 0, "magma": 1, "viridis": 2, "turbo": 3, "gray": 4}
 SPARSIFY_ALL, SPARSIFY_COUNT, SPARSIFY_COUNT_DEV, SPARSIFY_FRACTION = 0, 1, 2, 3
 # enum nconv_augment_crop
 AUGMENT_CROPS = {"random": 0, "center": 1, "min": 2, "max": 3}
+SPARSIFICATION_MAX_STEPS = 1024  # NCONV_SPARSIFICATION_MAX_STEPS
 
 EXPORTED = (
     "nconv_abi_version",
@@ -96,6 +97,8 @@ EXPORTED = (
     "nconv_depth_sparsify",
     "nconv_depth_occlusion",
     "nconv_frame_augment",
+    "nconv_depth_sparsification_workspace_bytes",
+    "nconv_depth_sparsification",
 )
 
 
@@ -232,6 +235,17 @@ class NconvFrameAugment(ctypes.Structure):
                 ("rgb_max", ctypes.c_float)]
 
 
+class NconvDepthSparsification(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("steps", ctypes.c_int),
+                ("pred", ctypes.c_void_p), ("pred_image_stride", ctypes.c_longlong),
+                ("pred_row_stride", ctypes.c_longlong), ("gt", ctypes.c_void_p),
+                ("gt_image_stride", ctypes.c_longlong), ("gt_row_stride", ctypes.c_longlong),
+                ("conf", ctypes.c_void_p), ("conf_image_stride", ctypes.c_longlong),
+                ("conf_row_stride", ctypes.c_longlong), ("gt_min", ctypes.c_float), ("gt_max", ctypes.c_float),
+                ("clamp_lo", ctypes.c_float), ("clamp_hi", ctypes.c_float), ("uncertainty", ctypes.c_int),
+                ("curves", ctypes.c_void_p), ("order", ctypes.c_void_p)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -353,6 +367,10 @@ def _declare(lib):
     lib.nconv_depth_occlusion.argtypes = [ctypes.POINTER(NconvDepthOcclusion), P, L, L, P, P, P, P]
     lib.nconv_frame_augment.restype = I
     lib.nconv_frame_augment.argtypes = [ctypes.POINTER(NconvFrameAugment), P]
+    lib.nconv_depth_sparsification_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_depth_sparsification_workspace_bytes.argtypes = [I, I, I, I]
+    lib.nconv_depth_sparsification.restype = I
+    lib.nconv_depth_sparsification.argtypes = [ctypes.POINTER(NconvDepthSparsification), P, ctypes.c_size_t, P]
 
 
 def lib():

@@ -1,5 +1,6 @@
 // capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
-// and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion and augment.
+// and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment and
+// sparsification curves.
 // Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
 // and calls its launcher (capi_common.h).
 #include "capi_common.h"
@@ -522,6 +523,53 @@ int nconv_frame_augment(const struct nconv_frame_augment* d, void* stream) {
                                          hw, kMask, 0};
     a.k = d->k, a.k_out = d->k_out, a.params = d->params, a.gains = d->gains;
     return launched(fn, launch_frame_augment, a, (hipStream_t)stream);
+}
+
+size_t nconv_depth_sparsification_workspace_bytes(int B, int H, int W, int steps) {
+    if (B <= 0 || H <= 0 || W <= 0 || steps < 1 || steps > NCONV_SPARSIFICATION_MAX_STEPS) return 0;
+    if ((long long)H * W >= (1LL << 31) || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::sparsification_workspace_bytes(B, H, W);
+}
+
+int nconv_depth_sparsification(const struct nconv_depth_sparsification* d, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    const char* fn = "nconv_depth_sparsification";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->pred || !d->gt || !d->conf) return fail(-22, fn, "null plane (pred, gt or conf)");
+    if (!d->curves) return fail(-22, fn, "null curves");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if (d->steps < 1 || d->steps > NCONV_SPARSIFICATION_MAX_STEPS) return fail(-22, fn, "steps must be in [1, 1024]");
+    if ((long long)H * W >= (1LL << 31))
+        return fail(-22, fn, "H * W must be below 2^31 (pixel numbers are int32)");
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    nconv::SparsificationArgs a{};
+    a.B = B, a.H = H, a.W = W;
+    auto view = [&](const char* name, const float* base, long long bs, long long rs, nconv::PlaneView& v) -> int {
+        if (const char* why = view_args(base, B, H, W, 4, bs, rs, 1LL << 31, 16, kViewHW, v))
+            return fail(-22, fn, (std::string(name) + ": " + why).c_str());
+        return 0;
+    };
+    if (int rc = view("pred", d->pred, d->pred_image_stride, d->pred_row_stride, a.p)) return rc;
+    if (int rc = view("gt", d->gt, d->gt_image_stride, d->gt_row_stride, a.g)) return rc;
+    if (int rc = view("conf", d->conf, d->conf_image_stride, d->conf_row_stride, a.c)) return rc;
+    if (!(d->gt_min >= 0.f) || !(d->gt_max >= 0.f) || !(d->clamp_lo >= 0.f) || !(d->clamp_hi >= 0.f))
+        return fail(-22, fn, "negative or NaN bound");
+    if (d->gt_min > 0.f && d->gt_max > 0.f && d->gt_min > d->gt_max) return fail(-22, fn, "gt_min > gt_max");
+    if (d->clamp_lo > 0.f && d->clamp_hi > 0.f && d->clamp_lo > d->clamp_hi)
+        return fail(-22, fn, "clamp_lo > clamp_hi");
+    if ((size_t)d->pred % 4 || (size_t)d->gt % 4 || (size_t)d->conf % 4 || (size_t)d->order % 4)
+        return fail(-22, fn, "pred / gt / conf / order not 4-byte aligned");
+    if ((size_t)d->curves % 8) return fail(-22, fn, "curves not 8-byte aligned");
+    if (!workspace || workspace_bytes < nconv::sparsification_workspace_bytes(B, H, W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    const float inf = __builtin_inff();
+    a.g_lo = d->gt_min, a.g_hi = d->gt_max > 0.f ? d->gt_max : inf;
+    a.c_lo = d->clamp_lo > 0.f ? d->clamp_lo : -inf, a.c_hi = d->clamp_hi > 0.f ? d->clamp_hi : inf;
+    a.steps = d->steps, a.uncertainty = d->uncertainty != 0;
+    a.curves = d->curves, a.order = d->order;
+    return launched(fn, nconv::launch_depth_sparsification, a, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

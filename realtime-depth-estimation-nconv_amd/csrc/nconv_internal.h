@@ -406,4 +406,18 @@ struct AugmentArgs {
 };
 int launch_frame_augment(const AugmentArgs& a, hipStream_t st, const char** why);
 
+// Sparsification curves of a confidence plane (nconv_depth_sparsification), sparsification.hip.
+struct SparsificationArgs {
+    PlaneView p, g, c;  // prediction, target, confidence: fp32, strides in elements (wide is not used)
+    int B, H, W;
+    float g_lo, g_hi;   // validity window of the target (absent bounds: 0, +inf)
+    float c_lo, c_hi;   // clamp window of the prediction (absent bounds: -inf, +inf)
+    int steps;          // J
+    int uncertainty;    // the plane is an uncertainty: larger is removed first
+    double* curves;     // (B, 2, J, 3)
+    int* order;         // (B, 2, H * W); null: skip
+};
+size_t sparsification_workspace_bytes(int B, int H, int W);
+int launch_depth_sparsification(const SparsificationArgs& a, void* workspace, hipStream_t st, const char** why);
+
 }  // namespace nconv
