@@ -1148,6 +1148,89 @@ size_t nconv_depth_sparsification_workspace_bytes(int B, int H, int W, int steps
 int nconv_depth_sparsification(const struct nconv_depth_sparsification* d, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* Added under ABI 27 (purely additive: one new entry point and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). Classical depth completion of a sparse depth plane: IP-Basic
+ * (Ku, Harakeh, Waslander, "In Defense of Classical Image Processing: Fast Depth Completion on the CPU",
+ * CRV 2018), its fill_in_fast made total (every input bit pattern has a defined result) and
+ * deterministic. The non-learned baseline beside the NConv networks, a pre-densifier, a quick picture.
+ * Every arithmetic operation below is one fp32 rounding in the stated order. T = 0.1f. In the inverted
+ * domain a pixel is valid iff v > T and empty iff v < T; as in the original, v == T is neither. For
+ * image b and pixel p with source value d_p:
+ *   0. invert   sample(p) holds when d_p is finite, d_p > T and (max_depth - d_p) > T. Where sample(p)
+ *               holds, v0 = max_depth - d_p; everywhere else v0 = +0.0f (NaN, +-inf, negatives, -0, too
+ *               small and too far values). From here on every value is finite and >= 0.
+ *   1. dilate   v1 = max of v0 over the in-image pixels of the kernel footprint, size s in {3, 5, 7},
+ *               r = s / 2: NCONV_IPBASIC_FULL |dy| <= r, |dx| <= r; NCONV_IPBASIC_CROSS dy == 0 || dx == 0
+ *               within r; NCONV_IPBASIC_DIAMOND |dy| + |dx| <= r. Pixels outside the image take no part in
+ *               any dilation.
+ *   2. close    v2 = erode(dilate(v1, full 5), full 5); erode is the min over the in-image window
+ *               pixels: pixels outside the image take no part.
+ *   3. fill     v3 = empty(v2) ? dilate(v2, full 7) : v2
+ *   4. only with extrapolate: per image and column x, top(x) = the smallest row y with
+ *               valid(v3[y, x]), 0 if the column has none;
+ *               v3e[y, x] = y < top(x) ? v3[top(x), x] : v3[y, x];
+ *               v4 = empty(v3e) ? dilate(v3e, full 31) : v3e. Without extrapolate, v4 = v3.
+ *   5. median   (if on) v5[p] = the 13th smallest of the 25 values of the 5 x 5 window of v4, coordinates
+ *               clamped to the image (replicate border), at every pixel. All inputs are finite and >= 0,
+ *               so the selection is exact. Off: v5 = v4.
+ *   6. blur     (NCONV_IPBASIC_BLUR_GAUSSIAN) separable, weights w = {0.0625, 0.25, 0.375, 0.25, 0.0625}
+ *               (OpenCV's fixed 5-tap kernel for ksize 5, sigma 0); the horizontal pass first into h,
+ *               then the vertical pass over h, each (((w0*a0 + w1*a1) + w2*a2) + w3*a3) + w4*a4, five
+ *               products and four sums, each rounded on its own. The products by 0.0625 and 0.25 are
+ *               exact, the one by 0.375 = 3 * 2^-3 is not (3 a needs two more bits than a), so
+ *               contracting to FMA does change bits: no contraction. Border reflect-101
+ *               (-1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3), folded until inside; a dimension of 1
+ *               maps every tap to 0. v6 = valid(v5) ? blurred : v5. NCONV_IPBASIC_BLUR_NONE: v6 = v5.
+ *               (The upstream script's bilateral blur needs exp and is not offered.)
+ *   7. back     out = valid(v6) ? max_depth - v6 : +0.0f; with keep_samples,
+ *               out = sample(p) ? d_p (bit for bit) : that. Without keep_samples IP-Basic does not
+ *               preserve its input samples: the median and the blur move them.
+ * The result is a function of the input alone: identical on every run. The source is only read.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_ipbasic`
+ * or nconv_depth_ipbasic_desc) */
+enum nconv_ipbasic_kernel {
+    NCONV_IPBASIC_FULL = 0,
+    NCONV_IPBASIC_CROSS = 1,
+    NCONV_IPBASIC_DIAMOND = 2
+};
+enum nconv_ipbasic_blur {
+    NCONV_IPBASIC_BLUR_NONE = 0,
+    NCONV_IPBASIC_BLUR_GAUSSIAN = 1
+};
+
+typedef struct nconv_depth_ipbasic {
+    int B, H, W;
+    const float* src;               /* fp32 view: B planes of H rows of W, 4-byte aligned          */
+    long long src_image_stride;     /* elements; ignored when B == 1                               */
+    long long src_row_stride;       /* elements, >= W                                              */
+    float max_depth;                /* finite, > 2 T (100 in ordinary use)                         */
+    int kernel_shape;               /* enum nconv_ipbasic_kernel (diamond in ordinary use)         */
+    int kernel_size;                /* 3, 5 or 7 (5 in ordinary use)                               */
+    int extrapolate;                /* != 0: stage 4                                               */
+    int median;                     /* != 0: stage 5                                               */
+    int blur;                       /* enum nconv_ipbasic_blur                                     */
+    int keep_samples;               /* != 0: the input samples come out bit for bit                */
+} nconv_depth_ipbasic_desc;
+
+/* dst: fp32 view of B planes of H rows of W with its own strides in elements, overwritten entirely.
+ * It must not overlap src: neighbours are read, so there is no in-place operation, and the host
+ * compares the two byte extents. Workspaces, needed with extrapolate only (else they may be NULL and
+ * are not touched): work_plane (B, H, W) contiguous fp32 (v3), work_top (B, W) int32 (top(x)), both
+ * overwritten, neither overlapping src or dst.
+ * Without extrapolate one kernel on `stream`: a workgroup stages a 64 x 64 tile and its halo of 14 in
+ * LDS, runs stages 0 to 7 between two LDS buffers and writes the tile once. With extrapolate three: one
+ * that resets work_top, stages 0 to 3 into work_plane with top(x) taken by an integer atomicMin on the
+ * row number (order-free), and the extrapolated read, the 31 x 31 fill and stages 5 to 7 from a tile
+ * with a halo of 19. No float atomics, no host synchronisation, no allocation, no waiting between
+ * workgroups: capturable. No byte outside the source view's extent is read.
+ * -EINVAL before any launch for a NULL descriptor / src / dst, B, H or W <= 0, B * H * W >= 2^31, an
+ * unknown kernel_shape, kernel_size or blur, a max_depth that is not finite or <= 2 T, src / dst /
+ * work_plane / work_top not 4-byte aligned, a src or dst view whose strides are smaller than its rows /
+ * images or whose image spans 2^31 bytes or more, a dst whose extent overlaps src's, and with
+ * extrapolate a NULL workspace or one that overlaps src or dst. */
+int nconv_depth_ipbasic(const struct nconv_depth_ipbasic* d, float* dst, long long dst_image_stride,
+                        long long dst_row_stride, float* work_plane, int* work_top, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,9 @@ SPARSIFY_ALL, SPARSIFY_COUNT, SPARSIFY_COUNT_DEV, SPARSIFY_FRACTION = 0, 1, 2, 3
 # enum nconv_augment_crop
 AUGMENT_CROPS = {"random": 0, "center": 1, "min": 2, "max": 3}
 SPARSIFICATION_MAX_STEPS = 1024  # NCONV_SPARSIFICATION_MAX_STEPS
+# enum nconv_ipbasic_kernel, enum nconv_ipbasic_blur
+IPBASIC_KERNELS = {"full": 0, "cross": 1, "diamond": 2}
+IPBASIC_BLURS = {None: 0, "none": 0, "gaussian": 1}
 
 EXPORTED = (
     "nconv_abi_version",
@@ -99,6 +102,7 @@ EXPORTED = (
     "nconv_frame_augment",
     "nconv_depth_sparsification_workspace_bytes",
     "nconv_depth_sparsification",
+    "nconv_depth_ipbasic",
 )
 
 
@@ -246,6 +250,14 @@ class NconvDepthSparsification(ctypes.Structure):
                 ("curves", ctypes.c_void_p), ("order", ctypes.c_void_p)]
 
 
+class NconvDepthIpbasic(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("src", ctypes.c_void_p),
+                ("src_image_stride", ctypes.c_longlong), ("src_row_stride", ctypes.c_longlong),
+                ("max_depth", ctypes.c_float), ("kernel_shape", ctypes.c_int), ("kernel_size", ctypes.c_int),
+                ("extrapolate", ctypes.c_int), ("median", ctypes.c_int), ("blur", ctypes.c_int),
+                ("keep_samples", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -371,6 +383,8 @@ def _declare(lib):
     lib.nconv_depth_sparsification_workspace_bytes.argtypes = [I, I, I, I]
     lib.nconv_depth_sparsification.restype = I
     lib.nconv_depth_sparsification.argtypes = [ctypes.POINTER(NconvDepthSparsification), P, ctypes.c_size_t, P]
+    lib.nconv_depth_ipbasic.restype = I
+    lib.nconv_depth_ipbasic.argtypes = [ctypes.POINTER(NconvDepthIpbasic), P, L, L, P, P, P]
 
 
 def lib():

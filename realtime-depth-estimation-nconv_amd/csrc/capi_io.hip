@@ -1,6 +1,6 @@
 // capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
-// and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment and
-// sparsification curves.
+// and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment,
+// sparsification curves and the IP-Basic baseline.
 // Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
 // and calls its launcher (capi_common.h).
 #include "capi_common.h"
@@ -570,6 +570,52 @@ int nconv_depth_sparsification(const struct nconv_depth_sparsification* d, void*
     a.steps = d->steps, a.uncertainty = d->uncertainty != 0;
     a.curves = d->curves, a.order = d->order;
     return launched(fn, nconv::launch_depth_sparsification, a, workspace, (hipStream_t)stream);
+}
+
+int nconv_depth_ipbasic(const struct nconv_depth_ipbasic* d, float* dst, long long dst_image_stride,
+                        long long dst_row_stride, float* work_plane, int* work_top, void* stream) {
+    const char* fn = "nconv_depth_ipbasic";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !dst) return fail(-22, fn, "null src or dst");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if (d->kernel_shape < NCONV_IPBASIC_FULL || d->kernel_shape > NCONV_IPBASIC_DIAMOND)
+        return fail(-22, fn, "unknown kernel_shape (enum nconv_ipbasic_kernel)");
+    if (d->kernel_size != 3 && d->kernel_size != 5 && d->kernel_size != 7)
+        return fail(-22, fn, "kernel_size must be 3, 5 or 7");
+    if (d->blur != NCONV_IPBASIC_BLUR_NONE && d->blur != NCONV_IPBASIC_BLUR_GAUSSIAN)
+        return fail(-22, fn, "unknown blur (enum nconv_ipbasic_blur)");
+    // T = 0.1f: below 2 T no depth is a sample
+    if (!(d->max_depth > 2.f * 0.1f) || d->max_depth == __builtin_inff())
+        return fail(-22, fn, "max_depth must be finite and above 2 T = 0.2");
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)work_plane % 4 || (size_t)work_top % 4)
+        return fail(-22, fn, "src / dst / work_plane / work_top not 4-byte aligned");
+    nconv::IpbasicArgs a{};
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(d->src, B, H, W, 4, d->src_image_stride, d->src_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.s))
+        return fail(-22, fn, (std::string("src: ") + why).c_str());
+    nconv::PlaneView dv{};
+    if (const char* why = view_args(dst, B, H, W, 4, dst_image_stride, dst_row_stride, kNoStrideLimit, 16, kViewPoints, dv))
+        return fail(-22, fn, (std::string("dst: ") + why).c_str());
+    // neighbours are read: the byte extents of the two views must be disjoint
+    const Extent se = view_extent(d->src, B, H, W, a.s.bs, 0, a.s.rs, 1, 4, "src");
+    const Extent de = view_extent(dst, B, H, W, dv.bs, 0, dv.rs, 1, 4, "dst");
+    if (de.overlaps(se)) return fail(-22, fn, "dst overlaps src (no in-place operation: neighbours are read)");
+    if (d->extrapolate) {
+        if (!work_plane || !work_top) return fail(-22, fn, "extrapolate without work_plane and work_top");
+        const Extent we = flat_extent(work_plane, 4LL * B * H * W, "work_plane");
+        const Extent te = flat_extent(work_top, 4LL * B * W, "work_top");
+        if (we.overlaps(se) || we.overlaps(de) || te.overlaps(se) || te.overlaps(de) || we.overlaps(te))
+            return fail(-22, fn, "a workspace overlaps src, dst or the other workspace");
+        a.work = work_plane, a.top = work_top;
+    }
+    a.max_depth = d->max_depth, a.shape = d->kernel_shape, a.r1 = d->kernel_size / 2;
+    a.extrapolate = d->extrapolate != 0, a.median = d->median != 0, a.blur = d->blur;
+    a.keep_samples = d->keep_samples != 0;
+    a.dst = dst, a.dbs = dv.bs, a.drs = dv.rs;
+    return launched(fn, nconv::launch_depth_ipbasic, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -420,4 +420,18 @@ struct SparsificationArgs {
 size_t sparsification_workspace_bytes(int B, int H, int W);
 int launch_depth_sparsification(const SparsificationArgs& a, void* workspace, hipStream_t st, const char** why);
 
+// Classical depth completion of a sparse plane, IP-Basic (nconv_depth_ipbasic), ipbasic.hip.
+struct IpbasicArgs {
+    PlaneView s;              // fp32, strides in elements
+    int B, H, W;
+    float max_depth;
+    int shape, r1;            // enum nconv_ipbasic_kernel; the custom kernel's radius 1 .. 3
+    int extrapolate, median, blur, keep_samples;
+    float* dst;               // strides in elements; disjoint from the source
+    long long dbs, drs;
+    float* work;              // (B, H, W) contiguous: v3 (extrapolate)
+    int* top;                 // (B, W): top(x), INT_MAX where the column has no valid pixel (extrapolate)
+};
+int launch_depth_ipbasic(const IpbasicArgs& a, hipStream_t st, const char** why);
+
 }  // namespace nconv
