@@ -31,9 +31,7 @@ static bool simple_geom(const nconv_layer& L) {
     return L.SH == 1 && L.SW == 1 && L.DH == 1 && L.DW == 1 && L.groups == 1 && L.KH == L.KW;
 }
 
-#ifndef NCONV_WG_MAX_BLOCKS
-#define NCONV_WG_MAX_BLOCKS 4096  // workspace bound; the launch uses at most one resident round
-#endif
+constexpr size_t kWgMaxBlocks = 4096;  // workspace bound; the launch uses at most one resident round
 
 enum Path { kTiled, kGeneric };
 
@@ -58,7 +56,7 @@ static int generic_chunks(const nconv_layer& L) {
 
 static size_t wg_blocks(const nconv_layer& L) {  // wgrad_tiled's 4 x 64 output tiles
     const size_t nt = (size_t)((L.Wo + 63) / 64) * ((L.Ho + 3) / 4) * L.B;
-    return nt < NCONV_WG_MAX_BLOCKS ? nt : NCONV_WG_MAX_BLOCKS;
+    return nt < kWgMaxBlocks ? nt : kWgMaxBlocks;
 }
 
 // tiled 3x3 / 5x5 layers with several input channels (Cin = 1 has a single-row A tile and stays

@@ -96,13 +96,12 @@ __global__ __launch_bounds__(NTH) void fwd_tiled(LayerDev d, float* __restrict__
                     for (int j = 0; j < C::P; ++j) acc[o][j] = __builtin_elementwise_fma(w2, v[j + kw], acc[o][j]);
                 }
     };
-#ifndef NCONV_TILED_UNROLL_CO
-#define NCONV_TILED_UNROLL_CO 2
-#endif
+    // (four channels per thread unrolled as well: no gain, profiles/r5_ab_small_layers_unrolled_co4.log)
+    constexpr int kUnrollCo = 2;
     auto fma_plane = [&](int ci, int bufi) {
         const f2* row = rowbase + bufi * kStride;
         const float* wr = wgt + (size_t)ci * K * K;  // weights of (ci, kh) are K contiguous floats
-        if constexpr (CO <= NCONV_TILED_UNROLL_CO) {
+        if constexpr (CO <= kUnrollCo) {
             // two output channels per thread (the channel-split small layers): the plane's 2 K*K
             // weights fit the SGPRs, so the rows are unrolled and every weight load issued up front
             // (their latency was exposed: < 1 wave per SIMD at the eighth resolution); down3 17 ->
@@ -395,15 +394,9 @@ static void go_tiled_cs(const LayerDev& d, float* y, float* yc, const TailArgs& 
 // a slice is whole waves, so its weights stay wave-uniform) and the layer spreads over the whole
 // chip. (Thresholds measured: a CS=1 limit of 1024 tiles against 2048 / 4096 / 8192 / never at
 // B=8 352x1216, one and two inference streams: profiles/r3_ab_fwd_cs.log.)
-#ifndef NCONV_CS1_TILES
-#define NCONV_CS1_TILES 1024
-#endif
-#ifndef NCONV_CS2_TILES
-#define NCONV_CS2_TILES 512
-#endif
-static int tiled_cs(long tiles16, int cout, int mode) {
-    (void)mode;
-    int cs = tiles16 >= NCONV_CS1_TILES ? 1 : tiles16 >= NCONV_CS2_TILES ? 2 : 4;
+constexpr long kCs1Tiles = 1024, kCs2Tiles = 512;
+static int tiled_cs(long tiles16, int cout) {
+    int cs = tiles16 >= kCs1Tiles ? 1 : tiles16 >= kCs2Tiles ? 2 : 4;
     while (cs > 1 && cout % cs) cs >>= 1;
     return cs;
 }
@@ -411,7 +404,7 @@ static int tiled_cs(long tiles16, int cout, int mode) {
 template <int CIN, int COUT, int K, int MODE, bool TAIL>
 static void go_tiled(const LayerDev& d, float* y, float* yc, const TailArgs& t, int gh, int gw, hipStream_t st) {
     const long tiles16 = (long)((gw + 31) / 32) * ((gh + 15) / 16) * d.L.B;
-    const int cs = (TAIL || MODE == NCONV_LOAD_THRESH) ? 1 : tiled_cs(tiles16, COUT, MODE);
+    const int cs = (TAIL || MODE == NCONV_LOAD_THRESH) ? 1 : tiled_cs(tiles16, COUT);
     if constexpr (!TAIL && COUT % 8 == 0) {
         if (cs == 4) return go_tiled_cs<CIN, COUT, K, MODE, TAIL, 4>(d, y, yc, t, gh, gw, st);
         if (cs == 2) return go_tiled_cs<CIN, COUT, K, MODE, TAIL, 2>(d, y, yc, t, gh, gw, st);

@@ -54,6 +54,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // TR (training): nconv1's outputs of the tile's own 16 x 32 pixels also go to HBM (the backward
 // reads them) and the pooled copies come with their argmax words (nconv_fwd_pooled's codes).
+// Where the time goes (B=8 352x1216 at 5 % density, 217 us; each part compiled out in turn, the
+// probes since removed; DESIGN.md section 5, no log under profiles/): nconv2's data sums ~103 us,
+// nconv1's nonzero taps ~41, the pooled copies ~11, the rest (staging, D2, epilogue, stores) ~62.
 template <bool TR>
 __global__ __launch_bounds__(kHT) __attribute__((amdgpu_waves_per_eu(5, 8))) void fwd_head_exact(LayerDev d2, TailArgs t, float* __restrict__ y,
                                                       float* __restrict__ yc) {
@@ -131,10 +134,8 @@ __global__ __launch_bounds__(kHT) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
             const bool valid = e < kHH * kHW;
             const bool in = valid && (unsigned)gr < (unsigned)H && (unsigned)gc < (unsigned)W;
             unsigned m = 0;
-#ifndef NCONV_HEAD_PROBE_NO_N1  // timing probe only (wrong results): no nconv1 taps
 #pragma unroll
             for (int kh = 0; kh < 5; ++kh) m |= (unsigned)((rowmask[(valid ? r : 0) + kh] >> c) & 31ull) << (5 * kh);
-#endif
             m = in ? m : 0u;
             // tap tp = 5 kh + kw of the window at halo pixel (r, c) is staged at sxb[35 kh + tp]
             const float* const sxb = sx + r * kSW + c;
@@ -227,9 +228,7 @@ __global__ __launch_bounds__(kHT) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
             }
         }
     };
-#ifndef NCONV_HEAD_PROBE_NO_N2  // timing probe only (wrong results): no nconv2 data sums
     sum_planes(accN);
-#endif
     __syncthreads();  // every wave is done reading the x * c planes
     if (!interior) {
         // edge tile: nconv2's zero padding truncates the window -- D2 = W2 * c1 as the unfused
@@ -330,9 +329,6 @@ __global__ __launch_bounds__(kHT) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
         for (int h = 0; h < 2; ++h) {
             st_f32(ry, so[h], yv[h]);
             st_f32(rc, so[h], cv[h]);
-#ifdef NCONV_HEAD_PROBE_NO_POOL  // timing probe only (wrong results): no pooled copies
-            continue;
-#endif
             if constexpr (TR) {  // the first maximum's slot too (the backward's routing)
                 // window (r, c) (r, c+1) (r+1, c) (r+1, c+1): lanes l, l^1, l^16, l^17 (torch order)
                 const float yb = shfl_xor16(yv[h]), cb = shfl_xor16(cv[h]);

@@ -35,7 +35,6 @@
 // is the fp32 accumulation, as in any fp32 convolution. The kernels are the same with NP = 3 parts
 // (three planes per operand, three B fragments per k-step) and nine MFMAs per {N, D} k-step,
 // smallest terms first.
-#include <cstdlib>
 #include "nconv_internal.h"
 
 namespace nconv {
@@ -89,10 +88,8 @@ __device__ __forceinline__ void split_parts(const float (&v)[N], VT (&out)[NP]) 
     }
 }
 
-constexpr unsigned kOOB = 0x80000000u;
 constexpr int kOutPitch = 36;  // floats per row of a wave's output-transpose region
 constexpr int kTrBytes = 4 * 16 * kOutPitch * 4;  // four waves' regions (y, then cout, through one)
-
 
 // One position's 8 channels of {x*c, c} into the planes of a tile (base = plane 0 of the
 // position's channel group): x*c parts in planes 0 .. NP-1, c parts in NP .. 2NP-1.
@@ -115,7 +112,6 @@ template <int CIN, int K, int MODE, int TH, int NP>
 struct MfStage {
     using C = MfCfg<CIN, K, TH, NP>;
     static constexpr bool UP = MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST;
-    static constexpr unsigned OOB = 0x80000000u;
     float xv[C::NE][CIN], cv[C::NE][CIN];
 
     __device__ __forceinline__ void load(const LayerDev& d, int b, int ih0, int iw0, int tid) {
@@ -128,13 +124,13 @@ struct MfStage {
             const int ih = ih0 + r, iw = iw0 + col;
             const bool in = e < C::NPOS && (unsigned)ih < (unsigned)L.H && (unsigned)iw < (unsigned)L.W;
             if constexpr (MODE == NCONV_LOAD_POOL2)
-                ga[k] = in ? (unsigned)((2 * ih) * L.a.W + 2 * iw) * 4u : OOB;
+                ga[k] = in ? (unsigned)((2 * ih) * L.a.W + 2 * iw) * 4u : kOOB;
             else
-                ga[k] = in ? (unsigned)(ih * L.a.W + iw) * 4u : OOB;
+                ga[k] = in ? (unsigned)(ih * L.a.W + iw) * 4u : kOOB;
             if constexpr (UP) {
                 const int sh = nearest_src(ih, L.b.H, L.H, d.up_scale_h);
                 const int sw = nearest_src(iw, L.b.W, L.W, d.up_scale_w);
-                gb[k] = in ? (unsigned)(sh * L.b.W + sw) * 4u : OOB;
+                gb[k] = in ? (unsigned)(sh * L.b.W + sw) * 4u : kOOB;
             }
         }
         // One buffer resource per source tensor of this image (all its channels; the host checks
@@ -155,7 +151,7 @@ struct MfStage {
                 const int so = ci * pa;
 #pragma unroll
                 for (int k = 0; k < C::NE; ++k) {
-                    const unsigned o2 = ga[k] == OOB ? OOB : ga[k] + row;
+                    const unsigned o2 = ga[k] == kOOB ? kOOB : ga[k] + row;
                     const f2 x0 = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rax, ga[k], so, 0));
                     const f2 x1 = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rax, o2, so, 0));
                     const f2 c0 = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rac, ga[k], so, 0));
@@ -218,105 +214,9 @@ struct MfStage {
     }
 };
 
-__device__ __forceinline__ int floor_div4(int v) { return v >> 2; }  // arithmetic shift: floor
-
-// Staging through LDS-DMA (buffer_load_dwordx4 ... lds): no registers hold the halo in flight and
-// one wave-instruction moves 1 KiB, four times the bytes of a dword load. The fp32 source rows are
-// copied as aligned 16-byte vectors (row width a multiple of 4 floats, so a vector is wholly in or
-// out of the image; out-of-image vectors carry an offset past the resource and land as zeros, the
-// convolution's padding): source a at the layer's resolution (IH rows x 10 vectors per channel),
-// and for the upsample-concat modes source b at its own half resolution (IH/2+1 rows x 6 vectors),
-// the exact 2x nearest upsampling being applied when the planes are formed. Sections (a.x, a.c,
-// b.x, b.c) are padded to whole 1-KiB pieces; LDS is lane-linear within a piece.
-template <int CIN, int K, int MODE, int TH, int NP>
-struct DmaStage {
-    using C = MfCfg<CIN, K, TH, NP>;
-    static constexpr bool UP = MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST;
-    static constexpr int CA = UP ? CIN / 2 : CIN, CB = UP ? CIN / 2 : 0;
-    static constexpr int NVA = 10, SRA = C::IH;            // source a: vectors per row, rows
-    static constexpr int NVB = 6, SRB = C::IH / 2 + 1;     // source b (half resolution)
-    static constexpr int PA = (CA * SRA * NVA + 63) / 64;  // 1-KiB pieces per tensor of source a
-    static constexpr int PB = UP ? (CB * SRB * NVB + 63) / 64 : 0;
-    static constexpr int NPC = 2 * PA + 2 * PB;  // pieces
-    static constexpr int BYTES = NPC * 1024;
-    static_assert(4 * NVA >= C::IW + 3 && 4 * NVB >= (C::IW + 1) / 2 + 4, "staged columns cover the halo");
-
-    static constexpr bool SELF_SYNC = true;
-    __device__ __forceinline__ void issue(const LayerDev& d, const TailArgs&, int b, int ih0, int iw0,
-                                          unsigned char* stage, int tid) const {
-        const nconv_layer& L = d.L;
-        const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll 1
-        for (int j = wave; j < NPC; j += 4) {  // wave-uniform piece index
-            const int sec = j < 2 * PA ? j / PA : 2 + (j - 2 * PA) / PB;
-            const int jj = sec < 2 ? j - sec * PA : j - 2 * PA - (sec - 2) * PB;
-            const bool a = sec < 2;
-            const nconv_src& sr = a ? L.a : L.b;
-            const int Cs = a ? CA : CB, SR = a ? SRA : SRB, NV = a ? NVA : NVB;
-            const int r0 = a ? ih0 : (ih0 >> 1), c0 = 4 * floor_div4(a ? iw0 : (iw0 >> 1));
-            const float* base = ((sec & 1) ? sr.c : sr.x) + (size_t)b * Cs * sr.H * sr.W;
-            const __amdgpu_buffer_rsrc_t rs = plane_rsrc(base, Cs * sr.H * sr.W * 4);
-            const int f = jj * 64 + lane;
-            const int ch = f / (SR * NV), rem = f - ch * (SR * NV), row = rem / NV, vec = rem - row * NV;
-            const int gr = r0 + row, gc = c0 + 4 * vec;
-            const bool ok = ch < Cs && (unsigned)gr < (unsigned)sr.H && (unsigned)gc < (unsigned)sr.W;
-            const unsigned go = ok ? (unsigned)((ch * sr.H + gr) * sr.W + gc) * 4u : kOOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                rs, (__attribute__((address_space(3))) void*)(stage + j * 1024), 16, (int)go, 0, 0, 0);
-        }
-    }
-
-    // Wait for this wave's pieces, then (all pieces landed) form the bf16 planes.
-    __device__ __forceinline__ void to_planes(const LayerDev& d, const TailArgs&, int ih0, int iw0, unsigned char* lds,
-                                              unsigned char* stage, int tid) const {
-        __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0)
-        __syncthreads();
-        const float* S = reinterpret_cast<const float*>(stage);
-        const int sha = iw0 - 4 * floor_div4(iw0);                   // column shift in source a rows
-        const int rb0 = ih0 >> 1, cb0 = 4 * floor_div4(iw0 >> 1);  // source b origin
-#pragma unroll
-        for (int k = 0; k < C::NE; ++k) {
-            const int e = tid + kMfThreads * k;
-            if (C::NE * kMfThreads != C::NPOS && e >= C::NPOS) continue;
-            const int r = e / C::IW, col = e - r * C::IW;
-            const int ia = r * (NVA * 4) + col + sha;
-            const int ib = (((ih0 + r) >> 1) - rb0) * (NVB * 4) + ((iw0 + col) >> 1) - cb0;
-#pragma unroll
-            for (int g = 0; g < C::G; ++g) {
-                float p[8], q[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = 8 * g + j;
-                    bool from_a = true;
-                    int cs = ci;
-                    if constexpr (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST) {
-                        from_a = ci < CA;
-                        cs = from_a ? ci : ci - CA;
-                    } else if constexpr (MODE == NCONV_LOAD_UPCAT_UP_FIRST) {
-                        from_a = ci >= CB;
-                        cs = from_a ? ci - CB : ci;
-                    }
-                    float xv, cv;
-                    if (from_a) {
-                        xv = S[cs * SRA * NVA * 4 + ia];
-                        cv = S[PA * 256 + cs * SRA * NVA * 4 + ia];
-                    } else {
-                        xv = S[2 * PA * 256 + cs * SRB * NVB * 4 + ib];
-                        cv = S[(2 * PA + PB) * 256 + cs * SRB * NVB * 4 + ib];
-                    }
-                    q[j] = cv;
-                    p[j] = xv * cv;
-                }
-                store_planes<C>(lds + g * C::NPL * C::PSTRIDE + e * 16, p, q);
-            }
-        }
-    }
-};
-
 // Fused head (nconv_fwd_head): nconv2's input (x1, c1) = nconv1(S, S > thresh) is computed here,
-// per tile, from the (TH+8) x 40 sparse-depth halo, so it never exists in HBM. nconv1 runs on the
-// vector ALU in exact fp32 (packed {N, D} FMAs, the same tap order as fwd_tiled's nconv1, so the
-// values equal the unfused layer's), then feeds the split-bf16 planes like a loaded input.
+// per tile, from the (TH+8) x 40 sparse-depth halo, so it never exists in HBM, and feeds the
+// split-bf16 planes like a loaded input.
 constexpr int kModeHead = 100;
 
 // One position's 4 channels (a bf16x4 half of the position's 16-byte slot) into the planes.
@@ -333,108 +233,10 @@ __device__ __forceinline__ void store_half_planes(unsigned char* base, const flo
     }
 }
 
-template <int TH, int NP>
-struct HeadStage {
-    using C = MfCfg<8, 5, TH, NP>;
-    static constexpr int SH = C::IH + 4, SW = C::IW + 4;  // nconv1's own 5x5 halo around the tile
-    static constexpr int NS = SH * SW, NES = (NS + kMfThreads - 1) / kMfThreads;
-    static constexpr int WOFF = NS * 8;                   // {S * c0, c0} pairs, then
-    static constexpr int BYTES = WOFF + 2 * 25 * 16;      // nconv1's weights [half][kw][kh][o4]
-    static constexpr bool SELF_SYNC = true;
-    float sv[NES];
-
-    // nconv1's weights into LDS once per workgroup (visible after to_planes' first barrier), in
-    // the order the column loop reads them: one broadcast float4 (4 output channels) per tap.
-    __device__ __forceinline__ void init(const TailArgs& t, unsigned char* stage, int tid) const {
-        if (tid < 200) {
-            const int half = tid / 100, rem = tid - 100 * half;
-            const int kw = rem / 20, kh = (rem / 4) % 5, o = rem % 4;
-            reinterpret_cast<float*>(stage + WOFF)[tid] = t.w1[(half * 4 + o) * 25 + kh * 5 + kw];
-        }
-    }
-
-    __device__ __forceinline__ void issue(const LayerDev& d, const TailArgs& t, int b, int ih0, int iw0,
-                                          unsigned char*, int tid) {
-        const int H = d.L.H, W = d.L.W;
-        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(t.s_in + (size_t)b * H * W, H * W * 4);
-#pragma unroll
-        for (int k = 0; k < NES; ++k) {
-            const int e = tid + kMfThreads * k;
-            const int r = e / SW, col = e - r * SW;
-            const int ih = ih0 - 2 + r, iw = iw0 - 2 + col;
-            const bool in = e < NS && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-            sv[k] = ld_f32(rs, in ? (unsigned)(ih * W + iw) * 4u : kOOB);
-        }
-    }
-
-    __device__ __forceinline__ void to_planes(const LayerDev& d, const TailArgs& t, int ih0, int iw0,
-                                              unsigned char* lds, unsigned char* stage, int tid) const {
-        f2* T = reinterpret_cast<f2*>(stage);
-#pragma unroll
-        for (int k = 0; k < NES; ++k) {
-            const int e = tid + kMfThreads * k;
-            const float c0 = sv[k] > t.thresh1 ? 1.0f : 0.0f;  // step1.py:53
-            if (NES * kMfThreads == NS || e < NS) T[e] = (f2){sv[k] * c0, c0};
-        }
-        __syncthreads();  // (also: every wave is done with the previous tile's planes)
-        // nconv1: wave w computes output channels 4 (w & 1) .. +3 for column quads — one staged
-        // column and 4 consecutive rows per lane, half of the (IH / 4) x 36 quads per wave pair.
-        // The weights come from LDS (broadcast reads; per-lane global weight loads were
-        // vector-memory reads the loop waited on each iteration together with the previous tile's
-        // outstanding stores, and scalar loads also stalled it); consecutive lanes read consecutive
-        // {x*c, c} pairs, so the window reads are free of LDS bank conflicts.
-        static_assert(C::IW == 36 && C::IH % 4 == 0, "36 staged columns, whole row quads");
-        const int H = d.L.H, W = d.L.W;
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, half = wave & 1;
-        constexpr int NQ = (C::IH / 4) * C::IW, PERW = (NQ + 1) / 2;
-        static_assert(PERW <= 64, "one quad per lane");
-        const int tq = (wave >> 1) * PERW + lane;
-        if (lane < PERW && tq < NQ) {
-            const int rq = tq / C::IW, c = tq - rq * C::IW, r0 = 4 * rq;
-            const f4* wl = reinterpret_cast<const f4*>(stage + WOFF) + half * 25;
-            f2 acc[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int o = 0; o < 4; ++o) acc[j][o] = (f2){0.f, 0.f};
-
-#pragma unroll 1
-            for (int kw = 0; kw < 5; ++kw) {
-                const f2* col = T + r0 * SW + c + kw;
-                f2 v[8];
-#pragma unroll
-                for (int m = 0; m < 8; ++m) v[m] = col[m * SW];
-#pragma unroll
-                for (int kh = 0; kh < 5; ++kh) {
-                    const f4 w4 = wl[kw * 5 + kh];
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) {
-                        const float w = w4[o];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[j][o] = __builtin_elementwise_fma((f2){w, w}, v[j + kh], acc[j][o]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = r0 + j;
-                const bool in = (unsigned)(ih0 + r) < (unsigned)H && (unsigned)(iw0 + c) < (unsigned)W;
-                float p[4], q[4];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    float xv, cv;
-                    nconv_epilogue(acc[j][o].x, acc[j][o].y, t.eps1, t.b1[half * 4 + o], t.s1[half * 4 + o], xv, cv);
-                    q[o] = in ? cv : 0.f;  // nconv2's zero padding outside the image
-                    p[o] = in ? xv * cv : 0.f;
-                }
-                store_half_planes<C>(lds + (r * C::IW + c) * 16 + half * 8, p, q);
-            }
-        }
-    }
-};
-
-// The fused head with nconv1 on the matrix cores as well (the default; -DNCONV_HEAD_NC1_VALU keeps
-// the exact-fp32 vector-ALU nconv1 above). GEMM per v_mfma_f32_16x16x32_bf16, per block of 16
+// The fused head's staging: nconv1 on the matrix cores as well, in the layer's split arithmetic.
+// (An exact-fp32 nconv1 on the vector ALU in this place, packed {N, D} FMAs with its weights
+// broadcast from LDS, was measured slower, the head 195 against 164 us at B=8 352x1216, and is
+// removed.) GEMM per v_mfma_f32_16x16x32_bf16, per block of 16
 // columns x 4 rows of nconv1's (IH x IW) output region: D[(o, s')][u] = sum_k A[(o, s')][k] B[k][u]
 // with k = (kw: the lane group, kh': 8 consecutive rows of the window), so the lane holding output
 // column u reads 8 consecutive rows of one staged column: the thresholded depth is staged
@@ -586,62 +388,45 @@ struct HeadStageMf {
 
 // Persistent: gridDim.x (a multiple of 8) workgroups walk the tiles; the next tile's halo loads
 // are in flight while the current one's MFMAs and epilogue run.
-#ifndef NCONV_MF_TH5
-#define NCONV_MF_TH5 8  // output rows per tile of the 5x5 layers
-#endif
-#ifndef NCONV_MF_TH_TAIL
+// The halo is staged through registers. (Staging it by LDS-DMA, buffer_load ... lds of 16-byte row
+// vectors with the planes formed from the staged fp32 rows, was measured slower at two workgroups
+// per CU, nconv2 198 against 179 us and the tail 272 against 169 us at B=8 352x1216, and is
+// removed.)
+constexpr int kMfTh5 = 8;  // output rows per tile of the 5x5 layers
 // output rows per tile of the fused nconv6+7 tail: 16 (two row pairs per wave; its LDS, without
 // the epilogue transposes, still fits two workgroups per CU): 151 vs 162 us at B=8 352x1216.
 // (nconv4/5 keep 8: at 16 their LDS admits one workgroup per CU, 50 vs 44 us.)
-#define NCONV_MF_TH_TAIL 16
-#endif
-#ifndef NCONV_MF_TH_HEAD
-#define NCONV_MF_TH_HEAD 8  // output rows per tile of the fused nconv1+nconv2 head
-#endif
-#ifndef NCONV_MFMA_WAVES
-#define NCONV_MFMA_WAVES 3  // waves per SIMD: 168 VGPRs (3 workgroups per CU) without spilling
-#endif
+constexpr int kMfThTail = 16;
+constexpr int kMfThHead = 8;  // output rows per tile of the fused nconv1+nconv2 head
+constexpr int kMfWaves = 3;   // waves per SIMD: 168 VGPRs (3 workgroups per CU) without spilling
 // POOL2 staging holds four values per element before pooling: 2 waves per SIMD (no spills)
-#ifndef NCONV_MFMA_HEAD_WAVES
-#define NCONV_MFMA_HEAD_WAVES 3  // fused head
-#endif
-#ifndef NCONV_MFMA_UP_WAVES
-#define NCONV_MFMA_UP_WAVES 2  // the 16-channel upsample-concat layers (nconv4/5/6): no spills
-#endif
+constexpr int kMfHeadWaves = 3;  // fused head
+constexpr int kMfUpWaves = 2;    // the 16-channel upsample-concat layers (nconv4/5/6): no spills
 // three-part (exact-product) kernels: three B fragments per k-step and 1.5x the staged planes
-#ifndef NCONV_MFMA_X9_WAVES
-#define NCONV_MFMA_X9_WAVES 2
-#endif
-template <int MODE, bool DMA, int NP>
+constexpr int kMfX9Waves = 2;
+template <int MODE, int NP>
 constexpr int mf_waves() {
-    return NP == 3 ? NCONV_MFMA_X9_WAVES
-           : MODE == kModeHead ? NCONV_MFMA_HEAD_WAVES
-           : DMA || MODE == NCONV_LOAD_POOL2 ? 2
-           : (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST) ? NCONV_MFMA_UP_WAVES
-                                                                                         : NCONV_MFMA_WAVES;
+    return NP == 3 ? kMfX9Waves
+           : MODE == kModeHead ? kMfHeadWaves
+           : MODE == NCONV_LOAD_POOL2 ? 2
+           : (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST) ? kMfUpWaves
+                                                                                         : kMfWaves;
 }
-template <int CIN, int K, int MODE, int TH, bool DMA, int NP>
-using StageOf = typename std::conditional<
-    MODE == kModeHead,
-#ifdef NCONV_HEAD_NC1_VALU
-    HeadStage<TH, NP>,
-#else
-    HeadStageMf<TH, NP>,
-#endif
-    typename std::conditional<DMA, DmaStage<CIN, K, MODE, TH, NP>, MfStage<CIN, K, MODE, TH, NP>>::type>::type;
+template <int CIN, int K, int MODE, int TH, int NP>
+using StageOf =
+    typename std::conditional<MODE == kModeHead, HeadStageMf<TH, NP>, MfStage<CIN, K, MODE, TH, NP>>::type;
 template <int CIN, int K, int MODE, int EPI, int TH, int NP>
-constexpr int mf_lds_bytes(bool dma) {
-    return MfCfg<CIN, K, TH, NP>::LDS_IN + (EPI == kEpiTail ? 0 : kTrBytes) +
-           (MODE == kModeHead ? StageOf<CIN, K, MODE, TH, false, NP>::BYTES
-                              : dma ? DmaStage<CIN, K, MODE, TH, NP>::BYTES : 0);
+constexpr int mf_lds_bytes() {
+    return MfCfg<CIN, K, TH, NP>::LDS_IN + (EPI == kEpiTail ? 0 : kTrBytes) + StageOf<CIN, K, MODE, TH, NP>::BYTES;
 }
-template <int CIN, int K, int MODE, int EPI, int TH, bool VEC, bool DMA, int NP>
-__global__ __launch_bounds__(kMfThreads) __attribute__((amdgpu_waves_per_eu(mf_waves<MODE, DMA, NP>(), mf_waves<MODE, DMA, NP>()))) void fwd_mfma(LayerDev d, float* __restrict__ y, float* __restrict__ yc,
+template <int CIN, int K, int MODE, int EPI, int TH, bool VEC, int NP>
+__global__ __launch_bounds__(kMfThreads) __attribute__((amdgpu_waves_per_eu(mf_waves<MODE, NP>(), mf_waves<MODE, NP>()))) void fwd_mfma(LayerDev d, float* __restrict__ y, float* __restrict__ yc,
                                                        TailArgs t) {
     using C = MfCfg<CIN, K, TH, NP>;
-    using Stage = StageOf<CIN, K, MODE, TH, DMA, NP>;
-    // input planes, (non-tail) four waves' output-transpose regions (y and cout), DMA staging
-    __shared__ __attribute__((aligned(16))) unsigned char lds[mf_lds_bytes<CIN, K, MODE, EPI, TH, NP>(DMA)];
+    using Stage = StageOf<CIN, K, MODE, TH, NP>;
+    // input planes, (non-tail) four waves' output-transpose regions (y and cout), the stage's own
+    // LDS (the fused head's staged depth and nconv1 weights)
+    __shared__ __attribute__((aligned(16))) unsigned char lds[mf_lds_bytes<CIN, K, MODE, EPI, TH, NP>()];
     unsigned char* const stage = lds + C::LDS_IN + (EPI == kEpiTail ? 0 : kTrBytes);
     const nconv_layer& L = d.L;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -915,8 +700,8 @@ __global__ __launch_bounds__(kMfThreads) __attribute__((amdgpu_waves_per_eu(mf_w
                 }
             }
         }
-        // every wave is done reading the planes before the next tile's are formed (DmaStage's own
-        // barrier, after its wait, does this there; a __syncthreads here would drain the DMA)
+        // every wave is done reading the planes before the next tile's are formed (HeadStageMf's
+        // to_planes has a barrier of its own between staging the depth and writing the planes)
         if constexpr (!Stage::SELF_SYNC) __syncthreads();
     };
 
@@ -937,57 +722,25 @@ int mfma_grid_blocks(int waves, int lds_bytes) {
     return (cus * (per_cu > 0 ? per_cu : 1) + 7) / 8 * 8;
 }
 
-template <int CIN, int K, int MODE, int EPI, int TH, bool DMA, int NP>
+template <int CIN, int K, int MODE, int EPI, int TH, int NP>
 void go_mfma(const LayerDev& d, float* y, float* yc, const TailArgs& t, int gh, int gw, hipStream_t st) {
     using C = MfCfg<CIN, K, TH, NP>;
     const int ntiles = ((gw + C::TW - 1) / C::TW) * ((gh + TH - 1) / TH) * d.L.B;
-    int grid = mfma_grid_blocks(mf_waves<MODE, DMA, NP>(), mf_lds_bytes<CIN, K, MODE, EPI, TH, NP>(DMA));
+    int grid = mfma_grid_blocks(mf_waves<MODE, NP>(), mf_lds_bytes<CIN, K, MODE, EPI, TH, NP>());
     if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
     if (gw % 4 == 0)
-        hipLaunchKernelGGL((fwd_mfma<CIN, K, MODE, EPI, TH, true, DMA, NP>), grid, dim3(kMfThreads), 0, st, d, y, yc, t);
+        hipLaunchKernelGGL((fwd_mfma<CIN, K, MODE, EPI, TH, true, NP>), grid, dim3(kMfThreads), 0, st, d, y, yc, t);
     else
-        hipLaunchKernelGGL((fwd_mfma<CIN, K, MODE, EPI, TH, false, DMA, NP>), grid, dim3(kMfThreads), 0, st, d, y, yc, t);
-}
-
-// LDS-DMA staging: rows of every source a multiple of 4 floats (16-B vectors never straddle a row
-// end), exact 2x upsampling of source b with 8 + 8 channels, per-image sources below 2 GiB.
-// Measured slower than register staging at two workgroups per CU (nconv2 198 vs 179 us, the tail
-// 272 vs 169 us at B=8 352x1216): compiled in only with -DNCONV_MFMA_DMA=1 (build-time experiment).
-#ifndef NCONV_MFMA_DMA
-#define NCONV_MFMA_DMA 0
-#endif
-bool dma_ok(const nconv_layer& L, int cin) {
-    if (L.load_mode != NCONV_LOAD_PLAIN && L.load_mode != NCONV_LOAD_UPCAT_SKIP_FIRST &&
-        L.load_mode != NCONV_LOAD_UPCAT_UP_FIRST)
-        return false;
-    const bool up = L.load_mode != NCONV_LOAD_PLAIN;
-    auto fine = [](const nconv_src& s) {
-        return s.W % 4 == 0 && ((uintptr_t)s.x % 16) == 0 && ((uintptr_t)s.c % 16) == 0 &&
-               (long long)s.C * s.H * s.W * 4 < (1LL << 31);
-    };
-    if (!fine(L.a)) return false;
-    if (!up) return L.a.C == cin && L.a.H == L.H && L.a.W == L.W;
-    return fine(L.b) && L.a.C == cin / 2 && L.b.C == cin / 2 && L.a.H == L.H && L.a.W == L.W && L.H == 2 * L.b.H &&
-           L.W == 2 * L.b.W;
-}
-
-template <int CIN, int K, int MODE, int EPI, int TH, int NP>
-void go_mfma_np(const LayerDev& d, float* y, float* yc, const TailArgs& t, int gh, int gw, hipStream_t st) {
-    if constexpr (MODE == NCONV_LOAD_POOL2 || NP != 2 || !NCONV_MFMA_DMA)
-        go_mfma<CIN, K, MODE, EPI, TH, false, NP>(d, y, yc, t, gh, gw, st);
-    else if (dma_ok(d.L, CIN))
-        go_mfma<CIN, K, MODE, EPI, TH, true, NP>(d, y, yc, t, gh, gw, st);
-    else
-        go_mfma<CIN, K, MODE, EPI, TH, false, NP>(d, y, yc, t, gh, gw, st);
+        hipLaunchKernelGGL((fwd_mfma<CIN, K, MODE, EPI, TH, false, NP>), grid, dim3(kMfThreads), 0, st, d, y, yc, t);
 }
 
 // NP = 2 split parts (bf16x3) or 3 (bf16x9, exact products) by the layer's math
 template <int CIN, int K, int MODE, int EPI, int TH>
 void go_mfma_any(const LayerDev& d, float* y, float* yc, const TailArgs& t, int gh, int gw, hipStream_t st) {
     if (d.L.math == NCONV_MATH_BF16X9)
-        go_mfma_np<CIN, K, MODE, EPI, TH, 3>(d, y, yc, t, gh, gw, st);
+        go_mfma<CIN, K, MODE, EPI, TH, 3>(d, y, yc, t, gh, gw, st);
     else
-        go_mfma_np<CIN, K, MODE, EPI, TH, 2>(d, y, yc, t, gh, gw, st);
+        go_mfma<CIN, K, MODE, EPI, TH, 2>(d, y, yc, t, gh, gw, st);
 }
 
 }  // namespace
@@ -995,16 +748,8 @@ void go_mfma_any(const LayerDev& d, float* y, float* yc, const TailArgs& t, int 
 int launch_fwd_head(const LayerDev& d2, const TailArgs& t, float* y, float* yc, hipStream_t st, const char** why) {
     // (16-row tiles recompute less of nconv1's halo but fit two workgroups per CU instead of three:
     // 228 vs 215 us at B=8 352x1216)
-    if (d2.L.math == NCONV_MATH_BF16X9)
-        go_mfma<8, 5, kModeHead, kEpiPool, NCONV_MF_TH_HEAD, false, 3>(d2, y, yc, t, d2.L.Ho, d2.L.Wo, st);
-    else
-        go_mfma<8, 5, kModeHead, kEpiPool, NCONV_MF_TH_HEAD, false, 2>(d2, y, yc, t, d2.L.Ho, d2.L.Wo, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    go_mfma_any<8, 5, kModeHead, kEpiPool, kMfThHead>(d2, y, yc, t, d2.L.Ho, d2.L.Wo, st);
+    return launch_status(why);
 }
 
 // True when the layer has a matrix-core kernel: matrix-core math, 8 output channels, 8 input
@@ -1033,9 +778,9 @@ bool launch_fwd_mfma(const LayerDev& d, float* y, float* yc, const TailArgs& t, 
     const int gh = tail ? t.out_h : L.Ho, gw = tail ? t.out_w : L.Wo;
     if (L.Cin == 8 && L.KH == 5 && L.load_mode == NCONV_LOAD_PLAIN && !tail) {
         if (pool)
-            go_mfma_any<8, 5, NCONV_LOAD_PLAIN, kEpiPool, NCONV_MF_TH5>(d, y, yc, t, gh, gw, st);
+            go_mfma_any<8, 5, NCONV_LOAD_PLAIN, kEpiPool, kMfTh5>(d, y, yc, t, gh, gw, st);
         else
-            go_mfma_any<8, 5, NCONV_LOAD_PLAIN, kEpiPlain, NCONV_MF_TH5>(d, y, yc, t, gh, gw, st);
+            go_mfma_any<8, 5, NCONV_LOAD_PLAIN, kEpiPlain, kMfTh5>(d, y, yc, t, gh, gw, st);
         return true;
     }
     if (L.Cin == 8 && L.KH == 5 && L.load_mode == NCONV_LOAD_POOL2 && !tail && !pool) {
@@ -1049,9 +794,9 @@ bool launch_fwd_mfma(const LayerDev& d, float* y, float* yc, const TailArgs& t, 
         }
         if (L.load_mode == NCONV_LOAD_UPCAT_UP_FIRST) {
             if (tail && L.math == NCONV_MATH_BF16X9)  // (16-row tiles of three-part planes: one workgroup per CU)
-                go_mfma_np<16, 3, NCONV_LOAD_UPCAT_UP_FIRST, kEpiTail, 8, 3>(d, y, nullptr, t, gh, gw, st);
+                go_mfma<16, 3, NCONV_LOAD_UPCAT_UP_FIRST, kEpiTail, 8, 3>(d, y, nullptr, t, gh, gw, st);
             else if (tail)
-                go_mfma_np<16, 3, NCONV_LOAD_UPCAT_UP_FIRST, kEpiTail, NCONV_MF_TH_TAIL, 2>(d, y, nullptr, t, gh, gw, st);
+                go_mfma<16, 3, NCONV_LOAD_UPCAT_UP_FIRST, kEpiTail, kMfThTail, 2>(d, y, nullptr, t, gh, gw, st);
             else
                 go_mfma_any<16, 3, NCONV_LOAD_UPCAT_UP_FIRST, kEpiPlain, 8>(d, y, yc, t, gh, gw, st);
             return true;

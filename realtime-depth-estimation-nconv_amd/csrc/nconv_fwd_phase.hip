@@ -75,6 +75,10 @@ __device__ __forceinline__ ChanSrc native_src(const LayerDev& d, int b, int ca) 
 // PAR = (output-grid origin offset - padding) & 1: the parity of the first input row / column of
 // the windows of even output rows / columns (nconv4 / nconv5: padding 1 -> 1; the tail: nconv6
 // padding 0 computed from grid offset -1 -> 1).
+// Where the tail's time goes (B=8 352x1216, 164.5 us; each FMA loop compiled out in turn, the
+// probes since removed; profiles/r6_probe_tail_split.log): without the native half's loops 59.3,
+// without the upsampled half's 108.6, without both 18.2 (staging, barriers, epilogue): the time is
+// proportional to the loops' FMA counts.
 template <int MODE, bool TAIL, int PAR>
 __global__ __launch_bounds__(kPT) void fwd_phase(LayerDev d, float* __restrict__ y, float* __restrict__ yc,
                                                  TailArgs t) {
@@ -169,15 +173,11 @@ __global__ __launch_bounds__(kPT) void fwd_phase(LayerDev d, float* __restrict__
             ts.store(tile, xa, ca, 0.f);
             __syncthreads();
             ts.load(native_src<MODE>(d, b, ci + 2 < kPCA ? ci + 2 : kPCA - 1), xa, ca);
-#ifndef NCONV_PHASE_PROBE_NO_NATIVE  // timing probe only (wrong results): no native-half FMAs
             fma_native(ci, 0);
-#endif
             ts.store(tile + kStride, xb, cb, 0.f);
             __syncthreads();
             ts.load(native_src<MODE>(d, b, ci + 3 < kPCA ? ci + 3 : kPCA - 1), xb, cb);
-#ifndef NCONV_PHASE_PROBE_NO_NATIVE
             fma_native(ci + 1, 1);
-#endif
         }
     }
 #pragma unroll 1
@@ -185,15 +185,11 @@ __global__ __launch_bounds__(kPT) void fwd_phase(LayerDev d, float* __restrict__
         ls.store(low, lx0, lc0_);
         __syncthreads();
         ls.load(d, b, ci + 2 < kPCB ? ci + 2 : kPCB - 1, lx0, lc0_);
-#ifndef NCONV_PHASE_PROBE_NO_UP  // timing probe only (wrong results): no upsampled-half FMAs
         fma_up(ci, 0);
-#endif
         ls.store(low + kPLStride, lx1, lc1);
         __syncthreads();
         ls.load(d, b, ci + 3 < kPCB ? ci + 3 : kPCB - 1, lx1, lc1);
-#ifndef NCONV_PHASE_PROBE_NO_UP
         fma_up(ci + 1, 1);
-#endif
     }
 
     // ---- epilogue ----

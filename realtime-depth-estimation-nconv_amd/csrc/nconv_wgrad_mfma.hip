@@ -63,12 +63,8 @@ struct WmCfg {
     static constexpr int CPW = (CIN + 3) / 4, OPW = COUT / 4;  // channels staged per wave
 };
 
-#ifndef NCONV_WM_WAVES
-#define NCONV_WM_WAVES 3
-#endif
-#ifndef NCONV_WM_STORE_STEP
-#define NCONV_WM_STORE_STEP 1  // after which k-step the next row's staging is stored (its loads' latency budget)
-#endif
+constexpr int kWmWaves = 3;      // waves per SIMD asked of the compiler (wgrad_mfma)
+constexpr int kWmStoreStep = 1;  // after which k-step the next row's staging is stored (its loads' latency budget)
 
 // Staging of one {gN, gD} row of a strip for wgrad_mfma / wgrad_mfma2: COUT channels x 64 + K-1
 // columns from column ow0 - (K-1), wave w taking channels w + 4 kk. A main pass (column = lane) per
@@ -287,7 +283,7 @@ struct GRowStager {
 // wgrad_mfma: the 16 -> 8 3x3 UpCat layers, with and without the fused nconv7 backward (T7); the
 // 8 -> 8 5x5 layers take wgrad_mfma2 below.
 template <int CIN, int COUT, int K, int MODE, bool T7 = false>
-__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(NCONV_WM_WAVES, 8))) void wgrad_mfma(
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kWmWaves, 8))) void wgrad_mfma(
     LayerDev d, BwdArgs a, float* part, int nstrip, int nseg, int seg_rows) {
     static_assert(CIN == 16 && COUT == 8 && K == 3 &&
                       (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST),
@@ -440,7 +436,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(NCONV_WM_WAV
                     for (int u = 0; u < C::NT; ++u)
                         acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[t], vb[u], acc[t][u], 0, 0, 0);
             }
-            if (s == NCONV_WM_STORE_STEP && more) {
+            if (s == kWmStoreStep && more) {
                 store_in(oh + 1 - L.PH + K - 1);
                 gs.store(L, a, grow + (buf ^ 1) * C::GBUF, C::GPART, oh + 1, true);
             }
@@ -514,14 +510,9 @@ struct Wm2Cfg {
     static_assert(COUT % 4 == 0 && CIN % 4 == 0, "channels staged four per pass");
 };
 
-#ifndef NCONV_WM2_WAVES
-#define NCONV_WM2_WAVES 3
-#endif
-#ifndef NCONV_WM2_SCHED
-#define NCONV_WM2_SCHED 1
-#endif
+constexpr int kWm2Waves = 3;  // waves per SIMD asked of the compiler (wgrad_mfma2)
 template <int CIN, int COUT, int K, int MODE, bool GP = false>
-__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(NCONV_WM2_WAVES, 8))) void wgrad_mfma2(
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kWm2Waves, 8))) void wgrad_mfma2(
     LayerDev d, BwdArgs a, float* part, int nstrip, int nseg, int seg_rows) {
     using C = Wm2Cfg<CIN, COUT, K>;
     __shared__ __attribute__((aligned(16))) float lds[C::LDS];
@@ -630,9 +621,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(NCONV_WM2_WA
 #pragma unroll
                         for (int u = 0; u < C::NT; ++u)
                             acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[t], vb[u], acc[t][u], 0, 0, 0);
-#if NCONV_WM2_SCHED
                     __builtin_amdgcn_sched_barrier(0);  // (operand reads of the next step not hoisted above)
-#endif
                 }
             }
             if (more) {
@@ -682,21 +671,15 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(NCONV_WM2_WA
 
 // ---- launchers --------------------------------------------------------------------------------------
 // Grid: 64-wide q strips (q = ow + kw spans Wo + K - 1 columns) x row segments x images,
-// at most `target` workgroups: NCONV_WM_ROUNDS resident rounds of the instantiation (CUs x blocks
+// at most `target` workgroups: kMfmaRounds resident rounds of the instantiation (CUs x blocks
 // per CU x rounds; a third, nearly empty round once cost nconv2's weight gradient a third of its
 // time). One round (longer row segments: less per-block prologue, fewer partial rows) for the
 // weight gradients that share the CUs with the input-gradient chain, two for the tail's (T7), which
 // starts the side stream: graphed training step 2.104 -> 2.064 ms same box (one round everywhere
 // 2.093, the tail alone at one round 2.137; profiles/r6_ab_wgrad_rounds.log). The workspace is
 // sized for the larger round count at the largest possible occupancy (kMfmaRoundsMax).
-#ifndef NCONV_WM_ROUNDS
-#define NCONV_WM_ROUNDS 1
-#endif
-#ifndef NCONV_WM_T7_ROUNDS
-#define NCONV_WM_T7_ROUNDS 2
-#endif
-constexpr int kMfmaRounds = NCONV_WM_ROUNDS, kMfmaMaxPerCu = 4;
-constexpr int kMfmaRoundsMax = NCONV_WM_T7_ROUNDS > NCONV_WM_ROUNDS ? NCONV_WM_T7_ROUNDS : NCONV_WM_ROUNDS;
+constexpr int kMfmaRounds = 1, kMfmaT7Rounds = 2, kMfmaMaxPerCu = 4;
+constexpr int kMfmaRoundsMax = kMfmaT7Rounds > kMfmaRounds ? kMfmaT7Rounds : kMfmaRounds;
 struct WmGrid {
     int nstrip, nseg, seg_rows;
     size_t nblk;
@@ -735,7 +718,7 @@ int go_wgrad_mfma(const LayerDev& d, const BwdArgs& a, float* part, hipStream_t 
         return launch_wm(wgrad_mfma2<CIN, COUT, K, MODE, GP>, kMfmaRounds, d, a, part, st);
     } else {
         static_assert(!GP, "pooled-gradient routing: the 8 -> 8 5x5 layers");
-        return launch_wm(wgrad_mfma<CIN, COUT, K, MODE, T7>, T7 ? NCONV_WM_T7_ROUNDS : kMfmaRounds, d, a, part, st);
+        return launch_wm(wgrad_mfma<CIN, COUT, K, MODE, T7>, T7 ? kMfmaT7Rounds : kMfmaRounds, d, a, part, st);
     }
 }
 

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Build an experimental variant of libnconv.so: tools/build_variant.sh OUTDIR -DMACRO=VAL ...
-# (load it with NCONV_LIB=OUTDIR/libnconv.so)
+# (load it with NCONV_LIB=OUTDIR/libnconv.so). The one -D switch the sources still read is
+# -DNCONV_IEEE_DIV (IEEE divisions in the NConv epilogues); the tuning values are constexpr
+# constants, so a variant of one of them is a source edit built here with no -D at all.
 set -e
 out=$1; shift
 root="$(cd "$(dirname "$0")/.." && pwd)"
