@@ -76,11 +76,11 @@ def r32(t):
     return None if t is None else t.float().double()
 
 
-def build_case(case, seed):
-    """float64 operands (xa, ca, xb, cb, w, b) of a LAYER_CASES entry at batch 2."""
+def build_case(case, seed, batch=2):
+    """float64 operands (xa, ca, xb, cb, w, b) of a LAYER_CASES entry at batch 2 (or `batch`)."""
     name, mode, cin, cout, k, pad, stride, dil, groups, a_shape, b_shape = case
     g = torch.Generator().manual_seed(seed)
-    xa, ca = rand_pair(g, 2, *a_shape, dtype=torch.float64)
+    xa, ca = rand_pair(g, batch, *a_shape, dtype=torch.float64)
     if mode == THRESH:
         xa = xa * (torch.rand(xa.shape, generator=g, dtype=torch.float64) < 0.3)
         ca = None
@@ -89,7 +89,7 @@ def build_case(case, seed):
         ca = torch.randint(0, 3, ca.shape, generator=g).double() * 0.5
     xb = cb = None
     if b_shape is not None:
-        xb, cb = rand_pair(g, 2, *b_shape, dtype=torch.float64)
+        xb, cb = rand_pair(g, batch, *b_shape, dtype=torch.float64)
     w = rand_weight(g, cout, cin // groups, k, k, torch.float64)
     b = torch.rand(cout, generator=g, dtype=torch.float64) * 0.1
     return xa, ca, xb, cb, w, b
@@ -106,6 +106,55 @@ PHASE_CASES = [
     ("up_p0", 4, 0, (8, 34, 72), (8, 17, 36)),
     ("up_p1", 4, 1, (8, 36, 66), (8, 18, 33)),
 ]
+
+
+# The channel-slice variants of the tiled exact-fp32 forward (nconv_fwd.hip go_tiled: fwd_tiled<..., CS>,
+# CS output-channel slices per tile). CS follows tiles16 = ceil(Wo / 32) * ceil(Ho / 16) * B:
+# CS = 1 from CS1_TILES, CS = 2 from CS2_TILES, CS = 4 below (test_fwd_bound_cpu pins the two
+# constants to the source). Forward only, exact fp32; not in LAYER_CASES, so the backward matrix
+# does not grow. The smallest shapes that reach each variant: 16 x 16 output tiles (241 x 481, one
+# row and one column past the 15th tile) at batch 2 (512 tiles) and batch 4 (1024 tiles).
+# CS = 4 needs no shapes of its own: every LAYER_CASES entry has a few dozen tiles. The 8 -> 1 1x1
+# layer (nconv7) and the THRESH layer always run CS = 1 (go_tiled) and are LAYER_CASES entries.
+# (cs, batch, LAYER_CASES-style entry)
+CS2_TILES, CS1_TILES = 512, 1024
+_SLICE_LAYERS = [
+    ("plain", PLAIN, 8, 8, 5, 2, 1, 1, 1, (8, 241, 481), None),
+    ("pool", POOL2, 8, 8, 5, 2, 1, 1, 1, (8, 482, 962), None),
+    ("upcat_skip", UPCAT_SKIP_FIRST, 16, 8, 3, 1, 1, 1, 1, (8, 241, 481), (8, 120, 240)),
+    ("upcat_up", UPCAT_UP_FIRST, 16, 8, 3, 1, 1, 1, 1, (8, 241, 481), (8, 120, 240)),
+]
+FWD_SLICE_CASES = [(cs, batch, (f"cs{cs}_{c[0]}",) + c[1:]) for cs, batch in ((2, 2), (1, 4)) for c in _SLICE_LAYERS]
+
+
+def case_out_hw(case):
+    """Output (Ho, Wo) of a LAYER_CASES-style entry."""
+    _, mode, _, _, k, pad, stride, dil, _, a_shape, _ = case
+    H, W = (a_shape[1] // 2, a_shape[2] // 2) if mode == POOL2 else a_shape[1:]
+    return tuple((n + 2 * pad - dil * (k - 1) - 1) // stride + 1 for n in (H, W))
+
+
+def tiles16(batch, Ho, Wo):
+    """go_tiled's tile count: 16-row, 32-column output tiles over the batch."""
+    return ((Wo + 31) // 32) * ((Ho + 15) // 16) * batch
+
+
+def expected_fwd_kernel(case, fwd_math):
+    """The forward kernel family nconv_plan must name for a LAYER_CASES-style entry launched without
+    phase weights, from the case alone (nconv_fwd.hip plan_fwd restated; never calls the library):
+    the matrix-core kernels under bf16x3 / bf16x9 for Cout 8, square kernel, stride 1, dilation 1,
+    groups 1 and 8 -> 8 5x5 PLAIN / POOL2 or 16 -> 8 3x3 UPCAT; else the tiled exact-fp32 kernel
+    for the DNET shapes; else the generic one."""
+    _, mode, cin, cout, k, _, stride, dil, groups, *_ = case
+    simple = stride == 1 and dil == 1 and groups == 1
+    shape = (cin, cout, k)
+    conv8 = shape == (8, 8, 5) and mode in (PLAIN, POOL2)
+    upcat = shape == (16, 8, 3) and mode in (UPCAT_SKIP_FIRST, UPCAT_UP_FIRST)
+    if simple and fwd_math in ("bf16x3", "bf16x9") and (conv8 or upcat):
+        return "mfma_" + fwd_math
+    head = shape == (1, 8, 5) and mode == THRESH
+    last = shape == (8, 1, 1) and mode == PLAIN
+    return "tiled_fp32" if simple and (conv8 or upcat or head or last) else "generic"
 
 
 # ------------------------------------------------------------------------------------------------
@@ -315,8 +364,144 @@ def assert_gradients_elementwise(what, problem, got, kappas, bwd_math="fp32", re
     return worst
 
 
-def load_kappa():
+@functools.lru_cache(maxsize=None)
+def _load_json(name):
     import json
     import os
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bwd_bound_kappa.json")) as fh:
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)) as fh:
         return json.load(fh)
+
+
+def load_kappa():
+    return _load_json("bwd_bound_kappa.json")
+
+
+# ------------------------------------------------------------------------------------------------
+# The element-wise forward criterion: |got - ref| <= kappa * A + 1e-30 per element of y and cout,
+# ref the float64 oracle on fp32-rounded operands (pool winners, the threshold mask and the nearest
+# upsample are then decided on identical values: no element is left out), A the majorant below,
+# kappa by the rule of kappa() above from tests/golden/fwd_bound_kappa.json (tools/fwd_kappa.py: the
+# reference's own float32 run measured against the same float64 oracle).
+# ------------------------------------------------------------------------------------------------
+FWD_LABELS = ("y", "cout")
+
+
+def nconv2d_forward_majorant(x, c, w, b, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups=1, eps=R.EPS):
+    """First-order error magnitudes of oracle.nconv_ref.nconv2d's two outputs in float64, every
+    factor replaced by its absolute value and every subtraction by an addition. With
+    Nabs = conv(|x c|, |w|), Dabs = conv(|c|, |w|), D = conv(c, w), s[o] = sum w[o], sabs[o] = sum |w[o]|:
+
+        A_y = Nabs / |D+eps| * (1 + Dabs / |D+eps|) + |b|        (y = N / (D+eps) + b)
+        A_c = Dabs / |s| * (1 + sabs / |s|)                      (cout = D / s, s summed in fp32 too)
+
+    so kappa * A is what a forward with relative error kappa per term may be off by. (x, c) are the
+    glue's outputs. Returns (A_y, A_c)."""
+    assert x.dtype == torch.float64
+    geo = (stride, pad, dil, groups)
+    aw = w.abs()
+    D = F.conv2d(c, w, None, *geo)
+    Nabs = F.conv2d((x * c).abs(), aw, None, *geo)
+    Dabs = F.conv2d(c.abs(), aw, None, *geo)
+    s = w.reshape(w.shape[0], -1).sum(-1).view(1, -1, 1, 1).abs()
+    sabs = aw.reshape(w.shape[0], -1).sum(-1).view(1, -1, 1, 1)
+    inv = 1 / (D + eps).abs()
+    A_y = Nabs * inv * (1 + Dabs * inv) + b.abs().view(1, -1, 1, 1)
+    A_c = Dabs / s * (1 + sabs / s)
+    return A_y, A_c
+
+
+class FwdProblem:
+    """One layer-forward comparison: fp32-rounded float64 operands and the geometry."""
+
+    def __init__(self, name, mode, ops, geom):
+        self.name, self.mode, self.ops, self.geom = name, mode, list(ops), geom
+        self.cin_g, self.k = ops[4].shape[1], ops[4].shape[2]
+
+    def outputs(self, dtype=torch.float64, eps=R.EPS):
+        """(y, cout) of the oracle's own op sequence in dtype, as float64."""
+        with torch.no_grad():
+            ops = [None if t is None else t.to(dtype) for t in self.ops]
+            x, c = glue(self.mode, *ops[:4])
+            return tuple(t.double() for t in R.nconv2d(x, c, ops[4], ops[5], *self.geom, eps=eps))
+
+    def majorant(self):
+        xa, ca, xb, cb, w, b = self.ops
+        with torch.no_grad():
+            x, c = glue(self.mode, xa, ca, xb, cb)
+            return nconv2d_forward_majorant(x, c, w, b, *self.geom)
+
+    def kappa_ref(self, ref=None, A=None):
+        """Per output max_i |err_i| / A_i of the oracle's float32 run against its float64 run."""
+        ref = self.outputs() if ref is None else ref
+        A = self.majorant() if A is None else A
+        return {lab: float(((g - r).abs() / (a + 1e-30)).max())
+                for lab, r, g, a in zip(FWD_LABELS, ref, self.outputs(torch.float32), A)}
+
+
+def layer_fwd_problem(case, batch=2):
+    """test_layer_forward's operands (seed 1234), fp32-rounded: the values the device receives."""
+    name, mode, cin, cout, k, pad, stride, dil, groups, *_ = case
+    ops = [r32(t) for t in build_case(case, 1234, batch)]
+    return FwdProblem(name, mode, ops, ((stride, stride), (pad, pad), (dil, dil), groups))
+
+
+def phase_fwd_inputs(case):
+    """test_upcat_phase_forward's float64 operands (one generator, seed 11, batch 3), unrounded."""
+    name, mode, pad, a_shape, b_shape = case
+    g = torch.Generator().manual_seed(11)
+    xa, ca = rand_pair(g, 3, *a_shape, dtype=torch.float64)
+    xb, cb = rand_pair(g, 3, *b_shape, dtype=torch.float64)
+    w = rand_weight(g, 8, 16, 3, 3, torch.float64)
+    b = torch.rand(8, generator=g, dtype=torch.float64) * 0.1
+    return xa, ca, xb, cb, w, b
+
+
+def phase_fwd_problem(case):
+    """test_upcat_phase_forward's operands, fp32-rounded."""
+    name, mode, pad, *_ = case
+    return FwdProblem(name, mode, [r32(t) for t in phase_fwd_inputs(case)], ((1, 1), (pad, pad), (1, 1), 1))
+
+
+def fwd_problem(kind, name):
+    """The FwdProblem of a LAYER_CASES ("layer"), PHASE_CASES ("phase") or FWD_SLICE_CASES ("slice")
+    entry, by name."""
+    if kind == "layer":
+        return layer_fwd_problem(next(c for c in LAYER_CASES if c[0] == name))
+    if kind == "phase":
+        return phase_fwd_problem(next(c for c in PHASE_CASES if c[0] == name))
+    cs, batch, case = next(e for e in FWD_SLICE_CASES if e[2][0] == name)
+    return layer_fwd_problem(case, batch)
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_budget(kind, name):
+    """(problem, float64 outputs, majorant) of a forward case, computed once and shared (read-only)
+    by the tests that need it: every fwd_math of a layer case, the CPU self-checks."""
+    prob = fwd_problem(kind, name)
+    return prob, prob.outputs(), prob.majorant()
+
+
+def assert_outputs_elementwise(what, problem, got, kappas, fwd_math="fp32", ref=None, A=None):
+    """The element-wise criterion on (y, cout). got: float64 CPU tensors; kappas: {label:
+    kappa_ref}; fwd_math: the arithmetic of the kernel that ran (bf16x3 adds its per-product bound;
+    bf16x9's products are exact and add nothing). Every element is compared. Prints and returns
+    the worst err / (kappa A) per output."""
+    ref = problem.outputs() if ref is None else ref
+    A = problem.majorant() if A is None else A
+    worst, bad = {}, []
+    for lab, r, a, g in zip(FWD_LABELS, ref, A, got):
+        kap = kappa(lab, kappas[lab], problem.cin_g, problem.k, fwd_math)
+        ratio, idx, n = elementwise_excess(g, r, a, kap)
+        assert n == r.numel(), f"{what} {lab}: {r.numel() - n} elements not comparable"
+        worst[lab] = ratio
+        if ratio > 1:
+            bad.append(f"{what} {lab} [{fwd_math}]: err / (kappa A) = {ratio:.3g} at {idx}, tile position "
+                       f"({idx[-2] % TILE[0]}, {idx[-1] % TILE[1]}); kappa {kap:.3e}, got {float(g[idx]):.9e}, "
+                       f"ref {float(r[idx]):.9e}, A {float(a[idx]):.3e}")
+    print(f"{what} [{fwd_math}] worst err/(kappa A): " + " ".join(f"{k}={v:.3f}" for k, v in worst.items()))
+    assert not bad, "\n".join(bad)
+    return worst
+
+
+def load_fwd_kappa():
+    return _load_json("fwd_bound_kappa.json")

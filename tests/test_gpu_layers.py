@@ -2,7 +2,11 @@
 oracle (tests/nconv_cases.oracle_layer = reference glue + models/step1.py:116-149) in float64.
 
 Tolerances (written here, from BASELINE.json's north star and SURVEY.md 8(c)):
-  forward  : elementwise |gpu - ref| <= 1e-4 * |ref| + 1e-5          (fp32 kernel vs fp64 oracle)
+  forward  : elementwise |gpu - ref| <= 1e-4 * |ref| + 1e-5          (fp32 kernel vs fp64 oracle), and per element
+             |gpu - ref| <= kappa * A + 1e-30 against the float64 oracle of the fp32-rounded operands:
+             A the forward majorant (nconv_cases.nconv2d_forward_majorant), kappa 4x what the
+             reference's own float32 run costs (tests/golden/fwd_bound_kappa.json, nconv_cases.kappa),
+             with nconv_plan's forward kernel asserted before the launch
   backward : max|gpu - ref| / max|ref| <= 1e-3 per gradient tensor     (SURVEY.md 8(c)), and per element
              |gpu - ref| <= kappa * A + 1e-30 against the float64 oracle of the fp32-rounded operands:
              A the gradient majorant (nconv_cases.nconv2d_backward_majorant), kappa 4x what the
@@ -51,8 +55,12 @@ def test_layer_forward(nconv_amd, gpu, case, fwd_math):
     _, _, cin, cout, k, pad, stride, dil, groups, *_ = case
     ry, rc = oracle_layer(mode, xa, ca, xb, cb, w, b, (stride, stride), (pad, pad), (dil, dil), groups)
     gw = _gpu(w, gpu)
-    y, c = nconv_amd.nconv_layer(_spec(nconv_amd, case), _gpu(xa, gpu), _gpu(ca, gpu), _gpu(xb, gpu),
-                                 _gpu(cb, gpu), gw, _gpu(b, gpu), _wsum(nconv_amd, gw))
+    t = [_gpu(xa, gpu), _gpu(ca, gpu), _gpu(xb, gpu), _gpu(cb, gpu), gw, _gpu(b, gpu), _wsum(nconv_amd, gw)]
+    # the kernel that will run (nconv_plan), against the case's own expectation: a bf16 request on a
+    # matrix-core shape must run that bf16 kernel, an fp32 one the tiled (DNET shapes) or generic kernel
+    want_kernel = NC.expected_fwd_kernel(case, fwd_math)
+    assert nconv_amd.nconv.kernel_plan(_spec(nconv_amd, case), *t)[0] == want_kernel, (name, fwd_math)
+    y, c = nconv_amd.nconv_layer(_spec(nconv_amd, case), *t)
     torch.cuda.synchronize()
     assert y.shape == ry.shape and c.shape == rc.shape
     for got, ref in ((y, ry), (c, rc)):
@@ -62,6 +70,41 @@ def test_layer_forward(nconv_amd, gpu, case, fwd_math):
         assert torch.isfinite(got).all()
         assert (err <= bound).all(), f"{name}: max err {err.max():.3e}, worst ratio {(err / bound).max():.3f}"
         print(f"{name} [{fwd_math}]: max rel err {(err / (ref.abs() + 1e-30)).max():.2e}")
+    # the element-wise budget, against float64 of the fp32-rounded operands (the values the device
+    # received; computed once per case); the kernel's arithmetic decides kappa's bf16x3 addend
+    prob, refs, A = NC.fwd_budget("layer", name)
+    NC.assert_outputs_elementwise(name, prob, (y.double().cpu(), c.double().cpu()), NC.load_fwd_kappa()["layer"][name],
+                                  fwd_math if want_kernel.startswith("mfma_") else "fp32", refs, A)
+
+
+@pytest.mark.parametrize("entry", NC.FWD_SLICE_CASES, ids=[e[2][0] for e in NC.FWD_SLICE_CASES])
+def test_layer_forward_channel_slices(nconv_amd, gpu, entry, monkeypatch):
+    """The tiled exact-fp32 forward's channel-slice variants (go_tiled: CS = 2 from 512 16 x 32
+    tiles, CS = 1 from 1024; CS = 4 is what every LAYER_CASES entry runs), per layer against the
+    float64 oracle of the fp32-rounded operands: 16 x 16 tiles, the last row and column of tiles
+    one pixel deep. nconv7's 8 -> 1 layer and the THRESH layer always run CS = 1 and are layer cases."""
+    monkeypatch.setattr(nconv_amd.nconv, "FORWARD_MATH", nconv_amd.nconv._MATH_NAMES["fp32"])
+    cs, batch, case = entry
+    name = case[0]
+    prob, refs, A = NC.fwd_budget("slice", name)
+    Ho, Wo = NC.case_out_hw(case)
+    tiles = NC.tiles16(batch, Ho, Wo)
+    lo, hi = {1: (NC.CS1_TILES, float("inf")), 2: (NC.CS2_TILES, NC.CS1_TILES)}[cs]
+    print(f"{name}: tiles16 = {tiles} (CS = {cs})")
+    assert lo <= tiles < hi, (name, tiles)
+    gl = [_gpu(v, gpu) for v in prob.ops]
+    t = gl[:4] + [gl[4], gl[5], _wsum(nconv_amd, gl[4])]
+    assert nconv_amd.nconv.kernel_plan(_spec(nconv_amd, case), *t)[0] == "tiled_fp32"
+    y, c = nconv_amd.nconv.layer_forward_raw(_spec(nconv_amd, case), *t)
+    torch.cuda.synchronize()
+    assert tuple(y.shape) == tuple(c.shape) == (batch, 8, Ho, Wo) == tuple(refs[0].shape)
+    got = (y.double().cpu(), c.double().cpu())
+    for g, ref in zip(got, refs):
+        err = (g - ref).abs()
+        bound = 1e-4 * ref.abs() + 1e-5
+        assert torch.isfinite(g).all()
+        assert (err <= bound).all(), f"{name}: max err {err.max():.3e}, worst ratio {(err / bound).max():.3f}"
+    NC.assert_outputs_elementwise(name, prob, got, NC.load_fwd_kappa()["slice"][name], "fp32", refs, A)
 
 
 @pytest.fixture(params=["bf16x3", "bf16x9", "fp32"])
@@ -362,6 +405,15 @@ def test_upcat_phase_forward(nconv_amd, gpu, case):
         bound = 1e-4 * ref.abs() + 1e-5
         assert (err <= bound).all(), f"{name}: max err {err.max():.3e}, worst ratio {(err / bound).max():.3f}"
     print(f"{name}: phase vs dense max rel {((y - yd).abs() / (yd.abs() + 1e-30)).max().item():.2e}")
+    # the element-wise budget on both paths, against float64 of the fp32-rounded operands (the same
+    # seed's values: asserted); the phase kernel's regrouped fp32 weights are rounding of
+    # non-negative terms and must fit
+    prob, refs, A = NC.fwd_budget("phase", name)
+    for mine, theirs in zip((xa, ca, xb, cb, w, b), prob.ops):
+        assert torch.equal(NC.r32(mine), theirs)
+    kap = NC.load_fwd_kappa()["phase"][name]
+    for what, outs in ((f"{name} phase", (y, c)), (f"{name} dense", (yd, cd))):
+        NC.assert_outputs_elementwise(what, prob, [o.double().cpu() for o in outs], kap, "fp32", refs, A)
 
 
 @pytest.mark.parametrize("case", PHASE_CASES, ids=[c[0] for c in PHASE_CASES])
