@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, _streams
 from ._lib import DENSE_1X1, DENSE_3X3, DENSE_CONV4X4_S2, DENSE_TRANSPOSED_4X4  # noqa: F401  (re-exported)
 
 
@@ -183,13 +183,6 @@ def relu_bias_bwd(g, out, g_masked, gbias):
 # gradient(s), joined before the node returns (1; 0 = serial). Joining once at the end of the
 # backward pass measured slower (43.3 -> 44.0 ms per guided step, profiles/r5_ab_guided_wgrad_join.log)
 WGRAD_STREAM = int(os.environ.get("NCONV_DENSE_WGRAD_STREAM", "1"))
-_WGRAD_STREAMS = {}
-
-
-def _wgrad_stream(device):
-    if device.index not in _WGRAD_STREAMS:
-        _WGRAD_STREAMS[device.index] = torch.cuda.Stream(device=device)
-    return _WGRAD_STREAMS[device.index]
 
 
 class DenseConvFn(torch.autograd.Function):
@@ -230,9 +223,8 @@ class DenseConvFn(torch.autograd.Function):
         w = weight.detach()
         side = None
         if need[2] and WGRAD_STREAM and (need[0] or (x1 is not None and need[1])):
-            cur, side = torch.cuda.current_stream(g.device), _wgrad_stream(g.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+            side = _streams.SideStream("dense_wgrad", g.device)
+            with torch.cuda.stream(side.fork()):
                 gw = wgrad(x0, x1, g, ctx.kind, ctx.stride, weight.shape)
         if need[0]:
             w0 = w if x1 is None else (w[:co] if tr else w[:, :co])
@@ -240,8 +232,7 @@ class DenseConvFn(torch.autograd.Function):
         if x1 is not None and need[1]:
             gx1 = dgrad(g, w[co:] if tr else w[:, co:], ctx.kind, ctx.stride, x1.shape)
         if side is not None:
-            cur.wait_stream(side)
-            gw.record_stream(cur)  # (made on the side stream, read on this one)
+            side.join(gw)  # (made on the side stream, read on this one)
         elif need[2]:
             gw = wgrad(x0, x1, g, ctx.kind, ctx.stride, weight.shape)
         return gx0, gx1, gw, gb, None, None, None

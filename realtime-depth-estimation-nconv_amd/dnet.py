@@ -20,11 +20,12 @@ import dataclasses
 import itertools
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib, dense, export, nconv
+from . import _lib, _streams, export, nconv
 from .nconv import (EnforcePos, NConv2d, WgradReduce, _require_device, head_weights, layer_backward,
                     layer_forward_head, layer_forward_pooled, layer_forward_raw, nconv_layer, phase_weights,
                     train_prologue, weight_prep)
@@ -36,19 +37,81 @@ LAYERS = ("nconv1", "nconv2", "nconv_down1", "nconv_down2", "nconv_down3", "ncon
 # Training forward in batch slices on this many streams (DNETFn.forward): the exact-fp32 pooled
 # graph with the fused head and tail only; 1 = one launch per layer over the whole batch
 TRAIN_FWD_STREAMS = int(os.environ.get("NCONV_TRAIN_FWD_STREAMS", "2"))
-_TRAIN_FWD_STREAMS = {}
+
+# Exact-fp32 training (DNETFn, pooled graph): the forward's head fused; nconv7's backward inside
+# nconv6's and nconv1's weight gradient inside nconv2's input gradient (nconv_bwd_ex tail / head);
+# the weight gradients on a second stream, concurrent with the input-gradient chain. Switches for
+# tests.
+FUSE_TAIL_BWD = True
+FUSE_HEAD_BWD = True
+FUSE_HEAD_FWD = True  # the training forward's nconv1 + nconv2 as the exact fused head (nconv_fwd_head)
+FUSE_TAIL_FWD = True  # ... and nconv6 + nconv7 as the fused tail (nconv_fwd_tail over nconv7's whole grid)
+
+# The training backward's weight gradients on one side stream (two round-robin streams measured
+# slower: 2.20 -> 2.26 ms per graphed step, profiles/r5_ab_two_wgrad_streams.log), except the last
+# layer's (nconv2's, WGRAD_LAST_MAIN): it runs on the main stream after that layer's input
+# gradient, which is the main stream's last kernel, instead of queueing behind the side stream's
+# backlog while the main stream idles
+WGRAD_STREAM = True
+WGRAD_LAST_MAIN = True
 
 
-def _train_fwd_streams(device, n):
-    key = (device.index, n)
-    if key not in _TRAIN_FWD_STREAMS:
-        _TRAIN_FWD_STREAMS[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-    return _TRAIN_FWD_STREAMS[key]
+def _exact_up(H, W):
+    """nconv6's skip input (nconv2's grid: the input's, H x W) is exactly twice nconv5's grid (the
+    pooled one, H // 2 x W // 2): the phase form of nconv6, the fused tails, the cropped output."""
+    return H % 2 == 0 and W % 2 == 0
 
 
-def _tail_exact_up(sp, S):
-    """nconv6's skip input (nconv2's grid, S's) is exactly twice nconv5's grid (the pooled one)."""
-    return S.shape[2] % 2 == 0 and S.shape[3] % 2 == 0
+def _layer_class(m):
+    """(hooks, usable) of one NConv2d: its forward pre-hooks are "none", "ours" (exactly this
+    package's softplus EnforcePos on the weight, which the prologue kernels apply themselves) or
+    "foreign" (anything else: run as hooks); usable: the weight is a contiguous fp32 device tensor."""
+    hooks, w = list(m._forward_pre_hooks.values()), m.weight
+    ours = len(hooks) == 1 and isinstance(hooks[0], EnforcePos) and hooks[0].name == "weight" \
+        and hooks[0].pos_fn.lower() == "softplus"
+    kind = "none" if not hooks else "ours" if ours else "foreign"
+    return kind, w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+
+
+def _wsum_views(weights, device):
+    """One s[o] vector per layer (weight.shape[0] elements), consecutive views of one buffer."""
+    buf = torch.empty(sum(w.shape[0] for w in weights), device=device, dtype=torch.float32)
+    return list(buf.split([w.shape[0] for w in weights]))
+
+
+class DNETArgs(NamedTuple):
+    """DNETFn's tensor arguments after S: layers = the nine (weight, bias, s[o]) in LAYERS order;
+    wph = the phase weights of nconv4/5/6 (a (3, 1024) tensor, DNET._phase_weights) or None; w21 =
+    the exact head's weights (None: built by the forward); wbox = the box weights of nconv4/5/6 (a
+    (3, 1024) tensor; None: built by the backward), the last two from DNET._train_prologue."""
+    layers: tuple
+    wph: Optional[torch.Tensor] = None
+    w21: Optional[torch.Tensor] = None
+    wbox: Optional[torch.Tensor] = None
+
+    def flatten(self):  # the fixed-arity form autograd sees (absent entries stay None)
+        return (*itertools.chain.from_iterable(self.layers), self.wph, self.w21, self.wbox)
+
+    @classmethod
+    def unflatten(cls, p):
+        return cls(tuple(tuple(p[3 * i:3 * i + 3]) for i in range(9)), *p[27:])
+
+
+def _batch_rows(full, B, b0, b1):
+    """The output allocator (nconv._outputs) of one batch slice's launches in the sliced training
+    forward: the i-th output of the slice's launches = rows b0:b1 of the full-batch tensor full[i],
+    which the first slice to ask for it allocates."""
+    it = itertools.count()
+
+    def rows(shapes, dtypes, device):
+        out = []
+        for sh, dt in zip(shapes, dtypes):
+            i = next(it)
+            if i == len(full):
+                full.append(torch.empty((B,) + tuple(sh[1:]), device=device, dtype=dt))
+            out.append(full[i][b0:b1])
+        return out
+    return rows
 
 
 def _train_fwd_chain(sp, W, S, w21, wph, crop, out, pooled=True):
@@ -79,7 +142,7 @@ def _train_fwd_chain(sp, W, S, w21, wph, crop, out, pooled=True):
         pools = ()
     x6, c6 = layer_forward_raw(sp[5], x4, c4, x5, c5, *W[5], out=out, wphase=w4)
     x7, c7 = layer_forward_raw(sp[6], x3, c3, x6, c6, *W[6], out=out, wphase=w5)
-    if pooled and FUSE_TAIL_FWD and w6 is not None and x2.shape[2:] == tuple(2 * v for v in x7.shape[2:]):
+    if pooled and FUSE_TAIL_FWD and w6 is not None and _exact_up(*S.shape[2:]):
         x8, c8, x9, c9 = _tail_train(sp[7], sp[8], x2, c2, x7, c7, W[7], W[8], w6, crop, out=out)
     elif crop is not None:
         raise RuntimeError("DNETFn: a cropped output needs the fused training tail")
@@ -91,9 +154,8 @@ def _train_fwd_chain(sp, W, S, w21, wph, crop, out, pooled=True):
 
 class DNETFn(torch.autograd.Function):
     """Autograd node of the whole 9-layer DNET graph (training path). The backward runs the layer
-    backwards in reverse order itself. Inputs: specs, capture (dict or None), S, then (weight, bias,
-    s[o]) of each layer in LAYERS order, then the phase weights; outputs: nconv7's (uncropped) y,
-    cout.
+    backwards in reverse order itself. Inputs: specs, capture (dict or None), crop, S, then
+    DNETArgs.flatten(); outputs: nconv7's (uncropped) y, cout.
 
     crop: None, or DNET's output size (h, w) when the fused training tail writes nconv7's output
     already cropped (DNET._tail_crop): the outputs are then the cropped (y, cout), and the backward
@@ -112,88 +174,61 @@ class DNETFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, specs, capture, crop, S, *p):
-        """p: (weight, bias, s[o]) of each layer, then the phase weights of nconv4/5/6 (a (3, 1024)
-        tensor, DNET._phase_weights) or None, then optionally the exact head's weights (None: built
-        here) and the box weights of nconv4/5/6 (a (3, 1024) tensor, None: built by the backward),
-        both from DNET._train_prologue."""
-        W = [p[3 * i:3 * i + 3] for i in range(9)]
-        wph = p[27] if len(p) > 27 and p[27] is not None else None
-        w21 = p[28] if len(p) > 28 else None
-        ctx.wbox = p[29] if len(p) > 29 else None
-        w6 = None if wph is None else wph[2]
+        """p: DNETArgs.flatten()."""
+        W, wph, w21, ctx.wbox = DNETArgs.unflatten(p)
         sp = specs
         pooled = _materialise_pool(S)
         ctx.crop = crop
         B = S.shape[0]
         nst = max(1, min(int(TRAIN_FWD_STREAMS), B))
-        if (pooled and FUSE_HEAD_FWD and FUSE_TAIL_FWD and w6 is not None and nst > 1 and
-                _tail_exact_up(sp, S)):
+        if (pooled and FUSE_HEAD_FWD and FUSE_TAIL_FWD and wph is not None and nst > 1 and
+                _exact_up(*S.shape[2:])):
             # the batch in nst slices, one stream each, every launch writing its rows of full-batch
-            # tensors (allocated by the first slice's launches): the slices' kernels overlap as the
-            # inference split's do; each frame's arithmetic is unchanged (bitwise the one-stream pass)
+            # tensors (allocated by the first slice's launches, on this stream): the slices' kernels
+            # overlap as the inference split's do; each frame's arithmetic is unchanged (bitwise the
+            # one-stream pass)
             if w21 is None:
                 w21 = head_weights(sp[0], sp[1], S, *W[0], *W[1])
-            bounds = [B * k // nst for k in range(nst + 1)]
             full = []
-            cur = torch.cuda.current_stream(S.device)
-            side = _train_fwd_streams(S.device, nst - 1)
-            for st in side:
-                st.wait_stream(cur)
-            res = None
-            for k, st in enumerate([cur] + side):
-                b0, b1 = bounds[k], bounds[k + 1]
 
-                def rows(shapes, dtypes, device, b0=b0, b1=b1, it=itertools.count()):
-                    # the i-th output of this slice's launches = rows b0:b1 of full-batch tensor i
-                    out = []
-                    for sh, dt in zip(shapes, dtypes):
-                        i = next(it)
-                        if i == len(full):
-                            full.append(torch.empty((B,) + tuple(sh[1:]), device=device, dtype=dt))
-                        out.append(full[i][b0:b1])
-                    return out
-                with torch.cuda.stream(st):
-                    r = _train_fwd_chain(sp, W, S[b0:b1], w21, wph, crop, rows)
-                res = r if res is None else res
-            for st in side:
-                cur.wait_stream(st)
+            def chain(b0, b1):  # (only the first slice's views are needed to name the full tensors)
+                r = _train_fwd_chain(sp, W, S[b0:b1], w21, wph, crop, _batch_rows(full, B, b0, b1))
+                return r if b0 == 0 else None
+            res = _streams.fork_join("train_fwd", S.device, [B * k // nst for k in range(nst + 1)], chain)[0]
             base = {t.data_ptr(): t for t in full}
-            (x1, c1, x2, c2, x3, c3, x4, c4, x5, c5, x6, c6, x7, c7, x8, c8, x9, c9, *pools) = [
-                base[t.data_ptr()] for t in res]
+            acts = [base[t.data_ptr()] for t in res]
         else:
-            (x1, c1, x2, c2, x3, c3, x4, c4, x5, c5, x6, c6, x7, c7, x8, c8, x9, c9, *pools) = \
-                _train_fwd_chain(sp, W, S, w21, wph, crop, None, pooled=pooled)
+            acts = _train_fwd_chain(sp, W, S, w21, wph, crop, None, pooled=pooled)
+        # acts: (x, c) of the nine layers' outputs, then the pooled copies and argmax codes
         if capture is not None:  # the three pooling stages' inputs (DNET.capture)
-            capture.update(down1=(x2.detach(), c2.detach()), down2=(x3.detach(), c3.detach()),
-                           down3=(x4.detach(), c4.detach()))
+            capture.update(down1=(acts[2].detach(), acts[3].detach()), down2=(acts[4].detach(), acts[5].detach()),
+                           down3=(acts[6].detach(), acts[7].detach()))
         ctx.specs = specs
         ctx.pooled = pooled
-        ctx.n_extra = len(p) - 27
-        ctx.save_for_backward(S, *p[:27], x1, c1, x2, c2, x3, c3, x4, c4, x5, c5, x6, c6, x7, c7, x8, c8, x9, c9,
-                              *pools)
+        ctx.save_for_backward(S, *p[:27], *acts)
+        x9, c9 = acts[16], acts[17]
         ctx.mark_non_differentiable(c9)
         ctx.set_materialize_grads(False)  # no zero-filled gradient for the never-used c9
         return x9, c9
 
     @staticmethod
     def backward(ctx, g9, gc9):
-        sv = ctx.saved_tensors
-        if g9 is None:  # (grads are not materialised)
-            g9 = torch.zeros_like(sv[44])
-        S, p, acts, pools = sv[0], sv[1:28], sv[28:46], sv[46:]
-        wbox = (None, None, None) if ctx.wbox is None else tuple(ctx.wbox)
-        W = [p[3 * i:3 * i + 3] for i in range(9)]
+        S, *sv = ctx.saved_tensors
+        W = [sv[3 * i:3 * i + 3] for i in range(9)]          # (weight, bias, s[o]) per layer
+        acts, pools = sv[27:45], sv[45:]                      # the layers' (x, c); the pooled graph's extras
         X = [None] + [(acts[2 * i], acts[2 * i + 1]) for i in range(9)]  # X[k] = output of layer k
-        need = ctx.needs_input_grad[2:]  # (capture, S, w1, b1, s1, ...)
-        gw = [torch.empty_like(W[i][0]) if need[2 + 3 * i] else None for i in range(9)]
-        gb = [torch.empty_like(W[i][1]) if need[3 + 3 * i] else None for i in range(9)]
+        if g9 is None:  # (grads are not materialised)
+            g9 = torch.zeros_like(X[9][0])
+        wbox = (None, None, None) if ctx.wbox is None else tuple(ctx.wbox)
+        need_S, *need = ctx.needs_input_grad[3:]  # (after specs, capture, crop: S, then w1, b1, s1, w2, ...)
+        gw = [torch.empty_like(W[i][0]) if need[3 * i] else None for i in range(9)]
+        gb = [torch.empty_like(W[i][1]) if need[3 * i + 1] else None for i in range(9)]
         e = torch.empty_like
         # input gradients: G[k] = (gx, gc) of layer k's output
         G = [None] * 10
         sp = ctx.specs
         red = WgradReduce()  # every layer's weight-gradient reduction in two launches at the end
-        cur = torch.cuda.current_stream(S.device)
-        side = _wgrad_stream(S.device) if (ctx.pooled and WGRAD_STREAM) else None
+        side = _streams.SideStream("dnet_wgrad", S.device) if (ctx.pooled and WGRAD_STREAM) else None
 
         def layer_bwd(spec, inputs, y, co, gy, gco, gin, gw_, gb_, **kw):
             # the weight gradient runs on the side stream, concurrent with this layer's input gradient
@@ -202,8 +237,7 @@ class DNETFn(torch.autograd.Function):
             if side is None or (gw_ is None and gb_ is None):
                 layer_backward(spec, inputs, y, co, gy, gco, gin, gw_, gb_, defer=red, **kw)
                 return
-            st = side
-            st.wait_stream(cur)
+            st = side.fork()
             tail, head = kw.pop("tail", None), kw.pop("head", None)
             layer_backward(spec, inputs, y, co, gy, gco, gin, None, None, defer=red, head=head,
                            tail=None if tail is None else tail[:7] + (None,) + tail[8:], **kw)  # (no gw7)
@@ -218,17 +252,11 @@ class DNETFn(torch.autograd.Function):
                       (*(ga or (None, None)), *(gb_ or (None, None))), gw[k - 1], gb[k - 1], accumulate=acc,
                       pool_grad=pool_grad, box=box)
 
-        def finish():
-            if side is not None:
-                cur.wait_stream(side)
-            red.run(S.device)
-
         G[2], G[7] = (e(X[2][0]), e(X[2][1])), (e(X[7][0]), e(X[7][1]))
-        exact_up = X[2][0].shape[2:] == tuple(2 * v for v in X[7][0].shape[2:])  # nconv6's phase form
         # (c9 is non-differentiable; nconv7's weight gradient is accumulated inside nconv6's weight-
         # gradient pass, so the fused form needs nconv6's gw or gb too)
-        if ctx.crop is not None or (FUSE_TAIL_BWD and ctx.pooled and exact_up and gw[8] is not None and
-                                    (gw[7] is not None or gb[7] is not None)):
+        if ctx.crop is not None or (FUSE_TAIL_BWD and ctx.pooled and _exact_up(*S.shape[2:]) and gw[8] is not None
+                                    and (gw[7] is not None or gb[7] is not None)):
             # nconv7's backward inside nconv6's (nconv_bwd_ex tail): its input gradient never reaches
             # HBM; its bias gradient is the sum of its output gradient (every output pixel, padding ring
             # included, as autograd's conv bias gradient), summed by the batched reduction. With the
@@ -258,19 +286,17 @@ class DNETFn(torch.autograd.Function):
             bwd(4, 0, 0, gp3, None, src_a=(p3x, p3c), spec=plain[1], pool_grad=(*gp4, a4))  # down2
             gp2 = (e(p2x), e(p2c))
             bwd(3, 0, 0, gp2, None, src_a=(p2x, p2c), spec=plain[0], pool_grad=(*gp3, a3))  # down1
-            if FUSE_HEAD_BWD and not need[1]:  # nconv2's input gradient feeds nconv1's weight gradient in-tile
-                args = (sp[1], (X[1][0], X[1][1], None, None, *W[1]), X[2][0], X[2][1], *G[2],
-                        (None, None, None, None), gw[1], gb[1])
-                kw = dict(pool_grad=(*gp2, a2), head=(sp[0], S, *W[0], gw[0], gb[0]))
-                if WGRAD_LAST_MAIN:  # the last layer's weight gradient after its input gradient, on this stream
-                    layer_backward(*args, defer=red, **kw)
-                else:
-                    layer_bwd(*args, **kw)
-                finish()
-                out = [None, None, None, None]
-                for i in range(9):
-                    out += [gw[i], gb[i], None]
-                return tuple(out + [None] * ctx.n_extra)
+        # nconv2's input gradient feeds nconv1's weight gradient in-tile: nconv1's backward inside nconv2's
+        head_bwd = ctx.pooled and FUSE_HEAD_BWD and not need_S
+        if head_bwd:
+            args = (sp[1], (X[1][0], X[1][1], None, None, *W[1]), X[2][0], X[2][1], *G[2],
+                    (None, None, None, None), gw[1], gb[1])
+            kw = dict(pool_grad=(*gp2, a2), head=(sp[0], S, *W[0], gw[0], gb[0]))
+            if WGRAD_LAST_MAIN:  # the last layer's weight gradient after its input gradient, on this stream
+                layer_backward(*args, defer=red, **kw)
+            else:
+                layer_bwd(*args, **kw)
+        elif ctx.pooled:
             G[1] = (e(X[1][0]), e(X[1][1]))
             bwd(2, 1, 0, G[1], None, pool_grad=(*gp2, a2))                 # nconv2
         else:
@@ -279,24 +305,15 @@ class DNETFn(torch.autograd.Function):
             bwd(3, 2, 0, G[2], None, acc=True)              # down1 -> nconv2's
             G[1] = (e(X[1][0]), e(X[1][1]))
             bwd(2, 1, 0, G[1], None)                        # nconv2
-        gS = e(S) if need[1] else None
-        layer_bwd(sp[0], (S, None, None, None, *W[0]), X[1][0], X[1][1], G[1][0], G[1][1],
-                  (gS, None, None, None), gw[0], gb[0])  # nconv1 (threshold: c0 has no gradient)
-        finish()
-        out = [None, None, None, gS]
-        for i in range(9):
-            out += [gw[i], gb[i], None]
-        return tuple(out + [None] * ctx.n_extra)
-
-
-# Exact-fp32 training (DNETFn, pooled graph): the forward's head fused; nconv7's backward inside
-# nconv6's and nconv1's weight gradient inside nconv2's input gradient (nconv_bwd_ex tail / head);
-# the weight gradients on a second stream, concurrent with the input-gradient chain. Switches for
-# tests.
-FUSE_TAIL_BWD = True
-FUSE_HEAD_BWD = True
-FUSE_HEAD_FWD = True  # the training forward's nconv1 + nconv2 as the exact fused head (nconv_fwd_head)
-FUSE_TAIL_FWD = True  # ... and nconv6 + nconv7 as the fused tail (nconv_fwd_tail over nconv7's whole grid)
+        gS = e(S) if need_S else None
+        if not head_bwd:
+            layer_bwd(sp[0], (S, None, None, None, *W[0]), X[1][0], X[1][1], G[1][0], G[1][1],
+                      (gS, None, None, None), gw[0], gb[0])  # nconv1 (threshold: c0 has no gradient)
+        if side is not None:
+            side.join()  # (the side stream's workspaces are handed over by WgradReduce.run)
+        red.run(S.device)
+        grads = itertools.chain.from_iterable((gw[i], gb[i], None) for i in range(9))
+        return (None, None, None, gS, *grads, None, None, None)  # (specs, capture, crop, S, layers, wph, w21, wbox)
 
 
 def _tail_train(sp6, sp7, x2, c2, x7, c7, W6, W7, w6, crop=None, out=None):
@@ -304,17 +321,8 @@ def _tail_train(sp6, sp7, x2, c2, x7, c7, W6, W7, w6, crop=None, out=None):
     (uncropped) output grid -- what the training backward reads (nconv_fwd_tail, crop0 = 0) -- or,
     with crop = (h, w), nconv7's output cropped as step1.py:94 (crop0 = 1). out: None or a callable
     as nconv._outputs takes."""
-    L = sp6.descriptor(x2, c2, x7, c7, *W6, w6)
-    (w7, b7, s7), p7 = W7, sp7.padding[0]
-    B, dev = x2.shape[0], x2.device
-    (H9, W9), crop0 = ((L.Ho + 2 * p7, L.Wo + 2 * p7), 0) if crop is None else (tuple(crop), 1)
-    sh8, sh9 = (B, sp6.cout, L.Ho, L.Wo), (B, 1, H9, W9)
-    x8, c8, x9, c9 = nconv._outputs(out, 4, (sh8, sh8, sh9, sh9), dev)
-    rc = _lib.lib().nconv_fwd_tail(_lib.ctypes.byref(L), _lib.ptr(w7), _lib.ptr(b7), _lib.ptr(s7), sp7.cin, p7,
-                                   sp7.eps, _lib.ptr(x9), _lib.ptr(c9), H9, W9, crop0, _lib.ptr(x8), _lib.ptr(c8),
-                                   _lib.stream_handle(dev))
-    _lib.check(rc, "nconv_fwd_tail")
-    return x8, c8, x9, c9
+    return nconv.layer_forward_tail(sp6, sp7, x2, c2, x7, c7, W6, W7, w6, out=out, crop0=0 if crop is None else 1,
+                                    size=None if crop is None else tuple(crop))
 
 
 class CropFn(torch.autograd.Function):
@@ -331,22 +339,6 @@ class CropFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return torch.nn.functional.pad(g, ctx.pad), None, None
-
-
-# The training backward's weight gradients on one side stream (two round-robin streams measured
-# slower: 2.20 -> 2.26 ms per graphed step, profiles/r5_ab_two_wgrad_streams.log), except the last
-# layer's (nconv2's, WGRAD_LAST_MAIN): it runs on the main stream after that layer's input
-# gradient, which is the main stream's last kernel, instead of queueing behind the side stream's
-# backlog while the main stream idles
-WGRAD_STREAM = True
-WGRAD_LAST_MAIN = True
-_WGRAD_STREAMS = {}
-
-
-def _wgrad_stream(device):
-    if device.index not in _WGRAD_STREAMS:
-        _WGRAD_STREAMS[device.index] = torch.cuda.Stream(device=device)
-    return _WGRAD_STREAMS[device.index]
 
 
 def _materialise_pool(S):
@@ -397,26 +389,40 @@ class DNET(nn.Module):
     # -- hooks ----------------------------------------------------------------------------------
     def _prologue(self, layers, S):
         """Run each layer's forward pre-hooks (EnforcePos) and compute s[o] for every layer."""
-        batched_sp, weights, wsums = [], [], []
+        batched_sp, weights = [], []
         for m in layers:
-            hooks = list(m._forward_pre_hooks.values())
-            ours = len(hooks) == 1 and isinstance(hooks[0], EnforcePos) and hooks[0].name == "weight" \
-                and hooks[0].pos_fn.lower() == "softplus"
-            if not ours:
-                for h in hooks:
+            kind, usable = _layer_class(m)
+            if kind == "foreign":
+                for h in list(m._forward_pre_hooks.values()):
                     h(m, (S,))
-            w = m.weight
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
+                usable = _layer_class(m)[1]  # (a hook may have replaced the weight)
+            if not usable:
                 raise RuntimeError(f"{type(m).__name__}.weight must be a contiguous fp32 device tensor")
-            weights.append(w.data)
-            batched_sp.append(ours and m.training)
-        buf = torch.empty(sum(w.shape[0] for w in weights), device=S.device, dtype=torch.float32)
-        off = 0
-        for w in weights:
-            wsums.append(buf[off:off + w.shape[0]])
-            off += w.shape[0]
+            weights.append(m.weight.data)
+            batched_sp.append(kind == "ours" and m.training)
+        wsums = _wsum_views(weights, S.device)
         weight_prep(weights, batched_sp, wsums)
         return wsums
+
+    def _merged_prologue_layers(self, layers, training):
+        """The layers' softplus flags for a one-launch prologue, or None where the separate path must
+        run: merged_prologue off, a forward pre-hook other than this package's softplus EnforcePos, a
+        weight that is not a contiguous fp32 device tensor, or (training False) a layer in training mode."""
+        if not self.merged_prologue:
+            return None
+        flags = []
+        for m in layers:
+            kind, usable = _layer_class(m)
+            if kind == "foreign" or not usable or (m.training and not training):
+                return None
+            flags.append(kind == "ours" and m.training)
+        return flags
+
+    def _phase_layers_ok(self):
+        """nconv4/5/6 run in the phase form: phase_upcat on, the exact-fp32 forward, and the three
+        layers 16 -> 8 channels 3x3 (the phase-weight kernels' geometry)."""
+        return self.phase_upcat and nconv.FORWARD_MATH == _lib.MATH_FP32 and all(
+            tuple(m.weight.shape) == (8, 16, 3, 3) for m in (self.nconv4, self.nconv5, self.nconv6))
 
     def _train_prologue(self, layers, S):
         """(wsums, phase weights, head weights, box weights) of the whole-graph training pass from
@@ -426,34 +432,20 @@ class DNET(nn.Module):
         tensors, or a matrix-core arithmetic. Phase / box weights are None when phase_upcat is off
         or the UpCat layers do not have the phase form's geometry; head weights None when the
         fused training head is off."""
-        if not self.merged_prologue or nconv.FORWARD_MATH != _lib.MATH_FP32 or not _materialise_pool(S):
+        if nconv.FORWARD_MATH != _lib.MATH_FP32 or not _materialise_pool(S):
             return None
-        sp = []
-        for m in layers:
-            hooks = list(m._forward_pre_hooks.values())
-            ours = len(hooks) == 1 and isinstance(hooks[0], EnforcePos) and hooks[0].name == "weight" \
-                and hooks[0].pos_fn.lower() == "softplus"
-            if not (len(hooks) == 0 or ours):
-                return None
-            w = m.weight
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                return None
-            sp.append(ours and m.training)
+        sp = self._merged_prologue_layers(layers, training=True)
+        if sp is None:
+            return None
         dev = S.device
         weights = [m.weight.data for m in layers]
-        buf = torch.empty(sum(w.shape[0] for w in weights), device=dev, dtype=torch.float32)
-        wsums, off = [], 0
-        for w in weights:
-            wsums.append(buf[off:off + w.shape[0]])
-            off += w.shape[0]
+        wsums = _wsum_views(weights, dev)
         head, w21 = None, None
         if FUSE_HEAD_FWD and self._head_shapes(layers[0], layers[1]):
             w21 = torch.empty(nconv.HEAD_WEIGHTS_FLOATS, device=dev, dtype=torch.float32)
             head = (0, 1, w21, nconv.sync_counter(dev))
         phase, wph, wbox = None, None, None
-        ls = (self.nconv4, self.nconv5, self.nconv6)
-        if self.phase_upcat and all(m.weight.shape[0] == 8 and m.weight.shape[1] == 16 and
-                                    tuple(m.weight.shape[2:]) == (3, 3) for m in ls):
+        if self._phase_layers_ok():
             wph = torch.empty((3, 1024), device=dev, dtype=torch.float32)
             wbox = torch.empty((3, nconv.BOX_WEIGHT_FLOATS), device=dev, dtype=torch.float32)
             phase = ([5, 6, 7], [8, 8, 0], list(wph), list(wbox))
@@ -474,8 +466,8 @@ class DNET(nn.Module):
         H, W = S.shape[2], S.shape[3]
         oh, ow = crop_hw(H, W, self.crop)
         l6, l7 = self.nconv6, self.nconv7
-        return (self.crop_in_tail and wph is not None and FUSE_TAIL_FWD and FUSE_TAIL_BWD and _materialise_pool(S) and H % 2 == 0
-                and W % 2 == 0 and tuple(l7.padding) == (2, 2) and oh >= H - 1 and ow >= W - 1
+        return (self.crop_in_tail and wph is not None and FUSE_TAIL_FWD and FUSE_TAIL_BWD and _materialise_pool(S)
+                and _exact_up(H, W) and tuple(l7.padding) == (2, 2) and oh >= H - 1 and ow >= W - 1
                 and (not l7.weight.requires_grad or l6.weight.requires_grad or l6.bias.requires_grad))
 
     # The eval-mode forward builds its weight-only prologue -- the normalisers, the exact head's
@@ -483,47 +475,25 @@ class DNET(nn.Module):
     # bitwise the three separate launches); False: the separate launches.
     merged_prologue = True
 
-    def _eval_prologue_ok(self, layers):
-        """Whether the one-launch eval prologue applies (see _eval_prologue)."""
-        if not self.merged_prologue:
-            return False
-        for m in layers:
-            hooks = list(m._forward_pre_hooks.values())
-            ours = len(hooks) == 1 and isinstance(hooks[0], EnforcePos) and hooks[0].name == "weight" \
-                and hooks[0].pos_fn.lower() == "softplus"
-            if m.training or not (len(hooks) == 0 or ours):
-                return False
-            w = m.weight
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                return False
-        return True
-
     def _eval_prologue(self, layers, S):
         """(wsums, phase weights or None, head weights or None) from one nconv_weight_prologue launch, or None where the separate path must run: merged_prologue off,
         a layer in training mode (EnforcePos then rewrites the weights first), a forward pre-hook
         other than this package's EnforcePos, or weights that are not contiguous fp32 device
         tensors."""
-        if not self._eval_prologue_ok(layers):
+        if self._merged_prologue_layers(layers, training=False) is None:
             return None
         dev = S.device
         weights = [m.weight.data for m in layers]
-        buf = torch.empty(sum(w.shape[0] for w in weights), device=dev, dtype=torch.float32)
-        wsums, off = [], 0
-        for w in weights:
-            wsums.append(buf[off:off + w.shape[0]])
-            off += w.shape[0]
+        wsums = _wsum_views(weights, dev)
         head = None
         l1, l2 = layers[0], layers[1]
         if nconv.FORWARD_MATH == _lib.MATH_FP32 and self._use_head(l1, l2):
             head = (l1.weight.data, l2.weight.data,
                     torch.empty(nconv.HEAD_WEIGHTS_FLOATS, device=dev, dtype=torch.float32))
         phase, wph = None, None
-        ls = (self.nconv4, self.nconv5, self.nconv6)
-        if self.phase_upcat and nconv.FORWARD_MATH == _lib.MATH_FP32 and all(
-                m.weight.shape[0] == 8 and m.weight.shape[1] == 16 and tuple(m.weight.shape[2:]) == (3, 3)
-                and m.weight.is_contiguous() for m in ls):
+        if self._phase_layers_ok():  # (their weights are contiguous: they are among `layers`)
             wph = torch.empty((3, 1024), device=dev, dtype=torch.float32)
-            phase = ([m.weight.data for m in ls], [8, 8, 0], list(wph))
+            phase = ([m.weight.data for m in (self.nconv4, self.nconv5, self.nconv6)], [8, 8, 0], list(wph))
         nconv.weight_prologue(weights, wsums, head=head, phase=phase)
         return wsums, wph, (head[2] if head is not None else None)
 
@@ -531,42 +501,24 @@ class DNET(nn.Module):
     def forward(self, S):
         if export.is_exporting():  # the export graph: the reference's own ops (export.py)
             return export.dnet(self, S)
-        _require_device(S, "DNET.forward")
-        if S.dim() != 4 or S.shape[1] != 1:
-            raise ValueError(f"DNET expects (B, 1, H, W) sparse depth, got {tuple(S.shape)}")
-        S = S.contiguous()
+        S = self._checked_input(S, "DNET.forward")
         layers = [getattr(self, n) for n in LAYERS]
-        grad = torch.is_grad_enabled() and (S.requires_grad or any(p.requires_grad for p in self.parameters()))
+        grad = self._records_grad(S)
         H, W = S.shape[2], S.shape[3]
         out_h, out_w = crop_hw(H, W, self.crop)
         if not grad and min(H, W) >= 16:
-            out = torch.empty((S.shape[0], 1, out_h, out_w), device=S.device, dtype=torch.float32)
-            pro = self._eval_prologue(layers, S)
-            if pro is None:
-                wsum, wph, w21 = self._prologue(layers, S), self._phase_weights(S.device), None
-            else:
-                wsum, wph, w21 = pro
-            self._infer_split(S, layers, wsum, out, wph, w21)
-            return out
+            return self._inference(S, layers, False)[0]
 
         (l1, l2, d1, d2, d3, l4, l5, l6, l7) = layers
         if grad and self.whole_graph_autograd and S.shape[0] > 0:
             specs = (l1.spec(_lib.THRESH, 0.01), l2.spec(), d1.spec(_lib.POOL2), d2.spec(_lib.POOL2),
                      d3.spec(_lib.POOL2), l4.spec(_lib.UPCAT_SKIP_FIRST), l5.spec(_lib.UPCAT_SKIP_FIRST),
                      l6.spec(_lib.UPCAT_UP_FIRST), l7.spec())
-            pro = self._train_prologue(layers, S)
-            if pro is None:
-                wsum = self._prologue(layers, S)
-                wph = self._phase_weights(S.device)
-                extra = (wph,)
-            else:
-                wsum, wph, w21, wbox = pro
-                extra = (wph, w21, wbox)
-            params = []
-            for m_, s_ in zip(layers, wsum):
-                params += [m_.weight, m_.bias, s_]
-            crop = (out_h, out_w) if self._tail_crop(S, extra[0]) else None
-            xo, _ = DNETFn.apply(specs, self.capture, crop, S, *params, *extra)
+            wsum, wph, w21, wbox = self._train_prologue(layers, S) or \
+                (self._prologue(layers, S), self._phase_weights(S.device), None, None)
+            args = DNETArgs(tuple((m_.weight, m_.bias, s_) for m_, s_ in zip(layers, wsum)), wph, w21, wbox)
+            crop = (out_h, out_w) if self._tail_crop(S, wph) else None
+            xo, _ = DNETFn.apply(specs, self.capture, crop, S, *args.flatten())
             return xo if crop is not None else CropFn.apply(xo, out_h, out_w)
 
         wsum = self._prologue(layers, S)
@@ -596,30 +548,39 @@ class DNET(nn.Module):
         cropped like the depth; 0 where the crop reaches nconv7's zero border. Inference only: it
         raises where gradients would be recorded, and takes the fused inference path (nconv_fwd_tail
         writes both), which needs min(H, W) >= 16."""
-        if torch.is_grad_enabled() and (S.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self._records_grad(S):
             raise RuntimeError("DNET.forward_with_confidence is inference only: call it under torch.no_grad() "
                                "(the output confidence has no backward)")
-        _require_device(S, "DNET.forward_with_confidence")
-        if S.dim() != 4 or S.shape[1] != 1:
-            raise ValueError(f"DNET expects (B, 1, H, W) sparse depth, got {tuple(S.shape)}")
+        S = self._checked_input(S, "DNET.forward_with_confidence")
         H, W = S.shape[2], S.shape[3]
         if min(H, W) < 16:
             raise ValueError(f"DNET.forward_with_confidence needs min(H, W) >= 16 (the fused inference path), got "
                              f"{H} x {W}")
-        S = S.contiguous()
-        layers = [getattr(self, n) for n in LAYERS]
-        out_h, out_w = crop_hw(H, W, self.crop)
-        out = torch.empty((S.shape[0], 1, out_h, out_w), device=S.device, dtype=torch.float32)
-        out_c = torch.empty_like(out)
-        pro = self._eval_prologue(layers, S)
-        if pro is None:
-            wsum, wph, w21 = self._prologue(layers, S), self._phase_weights(S.device), None
-        else:
-            wsum, wph, w21 = pro
+        return self._inference(S, [getattr(self, n) for n in LAYERS], True)
+
+    # -- inference ------------------------------------------------------------------------------
+    def _records_grad(self, S):
+        return torch.is_grad_enabled() and (S.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    @staticmethod
+    def _checked_input(S, what):
+        """S as the kernels read it: a contiguous fp32 (B, 1, H, W) device tensor, or an error."""
+        _require_device(S, what)
+        if S.dim() != 4 or S.shape[1] != 1:
+            raise ValueError(f"DNET expects (B, 1, H, W) sparse depth, got {tuple(S.shape)}")
+        return S.contiguous()
+
+    def _inference(self, S, layers, confidence):
+        """(depth, confidence or None) of the fused inference path on a checked S, min(H, W) >= 16: the
+        one-launch eval prologue, or the separate launches where it does not apply, then the layer chain."""
+        out = torch.empty((S.shape[0], 1, *crop_hw(S.shape[2], S.shape[3], self.crop)), device=S.device,
+                          dtype=torch.float32)
+        out_c = torch.empty_like(out) if confidence else None
+        wsum, wph, w21 = self._eval_prologue(layers, S) or \
+            (self._prologue(layers, S), self._phase_weights(S.device), None)
         self._infer_split(S, layers, wsum, out, wph, w21, out_c=out_c)
         return out, out_c
 
-    # -- inference ------------------------------------------------------------------------------
     # Exact-fp32 inference convolves the nearest-2x-upsampled half of nconv4/5/6's inputs at its
     # own resolution with phase weights (include/nconv.h nconv_layer.wphase; the kernel uses them
     # where the upsampling is exactly 2x); False: the 3x3 taps over the upsampled planes.
@@ -628,15 +589,12 @@ class DNET(nn.Module):
     def _phase_weights(self, device):
         """Phase weights of nconv4, nconv5 (cat(skip, up): up channels 8..15) and nconv6
         (cat(up, skip): 0..7) from the current weights, one launch; None when not in use."""
-        if not self.phase_upcat or nconv.FORWARD_MATH != _lib.MATH_FP32:
-            return None
-        ls = (self.nconv4, self.nconv5, self.nconv6)
-        if any(m.weight.shape[0] != 8 or m.weight.shape[1] != 16 or tuple(m.weight.shape[2:]) != (3, 3)
-               for m in ls):
+        if not self._phase_layers_ok():
             return None
         buf = torch.empty((3, 1024), device=device, dtype=torch.float32)
-        phase_weights([m.weight for m in ls], [8, 8, 0], list(buf))
+        phase_weights([m.weight for m in (self.nconv4, self.nconv5, self.nconv6)], [8, 8, 0], list(buf))
         return buf
+
     # Frames are independent, so the batch can be split over `inference_streams` HIP streams, each
     # running the whole layer chain on its share, so that one stream's kernels fill the partial
     # last round of the other's (and its small quarter / eighth-resolution layers overlap the other
@@ -682,13 +640,6 @@ class DNET(nn.Module):
             bounds[k] = min(max(int(round(B * acc / tot)), bounds[k - 1]), B)
         return bounds
 
-    def _side_streams(self, device, n):
-        key = (device.index, n)
-        cache = self.__dict__.setdefault("_stream_cache", {})
-        if key not in cache:
-            cache[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-        return cache[key]
-
     def _infer_split(self, S, layers, wsum, out, wph=None, w21=None, out_c=None):
         """The inference chain on batch slices, one stream each (the weight prologue once, on the
         current stream, before the fork: a prologue per stream measured slower, 16.3-16.5 k against
@@ -700,19 +651,8 @@ class DNET(nn.Module):
         if n == 1:
             self._infer(S, layers, wsum, out, wph, w21=w21, out_c=out_c)
             return
-        cur = torch.cuda.current_stream(S.device)
-        side = self._side_streams(S.device, n - 1)
-        for st in side:
-            st.wait_stream(cur)
-        for k, st in enumerate([cur] + side):
-            if bounds[k + 1] == bounds[k]:
-                continue
-            with torch.cuda.stream(st):
-                Sk = S[bounds[k]:bounds[k + 1]]
-                ck = None if out_c is None else out_c[bounds[k]:bounds[k + 1]]
-                self._infer(Sk, layers, wsum, out[bounds[k]:bounds[k + 1]], wph, w21=w21, out_c=ck)
-        for st in side:
-            cur.wait_stream(st)
+        _streams.fork_join("infer", S.device, bounds, lambda b0, b1: self._infer(
+            S[b0:b1], layers, wsum, out[b0:b1], wph, w21=w21, out_c=None if out_c is None else out_c[b0:b1]))
 
     def _infer(self, S, layers, wsum, out, wph=None, w21=None, out_c=None):
         """The inference chain on the current stream: each producer also writes the pooled input
@@ -768,15 +708,11 @@ class DNET(nn.Module):
         if out_c is not None and not (out_c.shape == out.shape and out_c.is_contiguous() and
                                       out_c.dtype == torch.float32 and out_c.device == out.device):
             raise RuntimeError("fused tail: out_c must be a contiguous fp32 tensor of out's shape and device")
-        L = l6.spec(_lib.UPCAT_UP_FIRST).descriptor(x1, c1, x23, c23, l6.weight, l6.bias, s6, w6)
         if tuple(l7.kernel_size) != (1, 1) or l7.padding[0] != l7.padding[1] or tuple(l7.stride) != (1, 1):
             raise RuntimeError("fused tail needs nconv7 = 1x1, stride 1, square padding")
-        rc = _lib.lib().nconv_fwd_tail(
-            _lib.ctypes.byref(L), _lib.ptr(l7.weight), _lib.ptr(l7.bias), _lib.ptr(s7), l7.in_channels,
-            l7.padding[0], l7.eps, _lib.ptr(out), _lib.ptr(out_c), out_h, out_w, 1, None, None,
-            _lib.stream_handle(x1.device))
-        _lib.check(rc, "nconv_fwd_tail")
-        return out
+        return nconv.layer_forward_tail(l6.spec(_lib.UPCAT_UP_FIRST), l7.spec(), x1, c1, x23, c23,
+                                        (l6.weight, l6.bias, s6), (l7.weight, l7.bias, s7), w6, crop0=1, y=out,
+                                        out_c=out_c)
 
 
 class SETP1_NCONV(nn.Module):

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import dense as D
+from . import _streams, dense as D
 from .dnet import SETP1_NCONV
 
 
@@ -334,7 +334,6 @@ def _use_dense(m, x):
 # The eval (dense) forward's encoders and decoder in this many batch slices, one stream each (every
 # frame's arithmetic is per frame: bitwise the one-stream pass); 1 = one launch per layer
 GUIDED_STREAMS = int(os.environ.get("NCONV_GUIDED_STREAMS", "2"))
-_GUIDED_STREAMS = {}
 
 
 def _dense_chain(m, rgb, sparse):
@@ -372,24 +371,10 @@ def _guided_forward_dense(m, rgb0, depth0, rgb1, depth1):
     n = max(1, min(int(GUIDED_STREAMS), B))
     if n == 1:
         return _dense_chain(m, rgb, sparse)
-    dev = rgb.device
-    prepare_dense_plans(m)  # on cur, before the side streams' wait_stream(cur)
-    if (dev.index, n) not in _GUIDED_STREAMS:
-        _GUIDED_STREAMS[(dev.index, n)] = [torch.cuda.Stream(device=dev) for _ in range(n - 1)]
-    side = _GUIDED_STREAMS[(dev.index, n)]
-    cur = torch.cuda.current_stream(dev)
-    for st in side:
-        st.wait_stream(cur)
-    bounds = [B * k // n for k in range(n + 1)]
-    parts = []
-    for k, st in enumerate([cur] + side):
-        with torch.cuda.stream(st):
-            parts.append(_dense_chain(m, rgb[bounds[k]:bounds[k + 1]], sparse[bounds[k]:bounds[k + 1]]))
-    for st in side:
-        cur.wait_stream(st)
-    for part in parts[1:]:  # the side streams' outputs are read on cur (under capture the
-        for t in part:      # allocator holds such blocks until the capture ends)
-            t.record_stream(cur)
+    prepare_dense_plans(m)  # on the current stream, before the fork
+    # (fork_join hands the side streams' outputs over to the current stream, which reads them)
+    parts = _streams.fork_join("guided", rgb.device, [B * k // n for k in range(n + 1)],
+                               lambda b0, b1: _dense_chain(m, rgb[b0:b1], sparse[b0:b1]))
     return tuple(torch.cat([part[i] for part in parts], dim=0) for i in range(4))
 
 

@@ -295,6 +295,29 @@ def layer_forward_head(spec1: LayerSpec, spec2: LayerSpec, S, w1, b1, s1, w2, b2
     return (y, co, py, pc, arg, y1, c1) if train else (y, co, py, pc)
 
 
+def layer_forward_tail(spec6: LayerSpec, spec7: LayerSpec, xa, ca, xb, cb, W6, W7, w6, out=None, crop0=0, size=None,
+                       y=None, out_c=None):
+    """nconv_fwd_tail: the UPCAT layer nconv6 (W6 = (weight, bias, s), phase weights w6 or None) and
+    its 1x1 consumer nconv7 (W7) in one launch. No autograd. Returns (y6, cout6, y7, cout7) -- written
+    as `out` says (_outputs) -- with nconv7's outputs over its whole grid, or with size = (h, w) the
+    window of that size from grid row / column crop0 (DNET's crop: crop0 = 1). y given (the inference
+    form): the window of y's size is written into y, its confidence into out_c if given, and nconv6's
+    outputs never reach HBM; returns y."""
+    L = spec6.descriptor(xa, ca, xb, cb, *W6, w6)
+    (w7, b7, s7), p7 = W7, spec7.padding[0]
+    if y is not None:
+        y6, c6, y7, c7, (H7, W7_) = None, None, y, out_c, y.shape[2:]
+    else:
+        H7, W7_ = (L.Ho + 2 * p7, L.Wo + 2 * p7) if size is None else size
+        sh6, sh7 = (L.B, spec6.cout, L.Ho, L.Wo), (L.B, 1, H7, W7_)
+        y6, c6, y7, c7 = _outputs(out, 4, (sh6, sh6, sh7, sh7), xa.device)
+    rc = _lib.lib().nconv_fwd_tail(_lib.ctypes.byref(L), _lib.ptr(w7), _lib.ptr(b7), _lib.ptr(s7), spec7.cin, p7,
+                                   spec7.eps, _lib.ptr(y7), _lib.ptr(c7), H7, W7_, crop0, _lib.ptr(y6), _lib.ptr(c6),
+                                   _lib.stream_handle(xa.device))
+    _lib.check(rc, "nconv_fwd_tail")
+    return y if y is not None else (y6, c6, y7, c7)
+
+
 class NConvLayerFn(torch.autograd.Function):
     """Autograd node of one fused NConv layer (glue + NConv2d.forward), kernels in libnconv."""
 

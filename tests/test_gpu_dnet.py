@@ -323,6 +323,26 @@ def test_inference_streams_split_matches_one_stream(nconv_amd, gpu, n):
     assert torch.equal(a, b) and torch.equal(a, c)
 
 
+@pytest.mark.parametrize("B,shares,bounds", [(1, None, [0, 1]), (2, (100, 1), [0, 2, 2]), (2, (1, 100), [0, 0, 2])])
+def test_inference_split_with_an_empty_slice(nconv_amd, gpu, B, shares, bounds):
+    """Two configured inference streams where a slice holds no frame -- B = 1 (one stream used), or
+    shares that round one slice to zero frames (the second stream idle; or the first, every frame
+    on the side stream) -- write the same bits as one stream (16 x 16: the fused path's smallest)."""
+    net = make_net(nconv_amd, "generalized", gpu)
+    d = net.d_net
+    S = sparse_depth(torch.Generator().manual_seed(41), B, 16, 16, density=0.3).to(gpu)
+    with torch.no_grad():
+        d.inference_streams = 1
+        a, ac = net.forward_with_confidence(S)
+        d.inference_streams, d.inference_shares = 2, shares
+        assert d.split_bounds(B, d._n_streams(B), shares, 2) == bounds
+        b, bc = net.forward_with_confidence(S)
+        c = net(S)
+        torch.cuda.synchronize()
+    assert a.shape == (B, 1, 16, 16) and torch.isfinite(a).all()
+    assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(ac, bc)
+
+
 # ---- full-size configurations (BASELINE.json configs[1] and configs[4]) ----------------------------
 _ORACLE_CACHE = {}
 

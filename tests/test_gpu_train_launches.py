@@ -233,3 +233,56 @@ def test_dnet_train_wgrad_stream_placement_bitwise(nconv_amd, gpu, B, H, W, crop
         assert set(ga) == set(gb) and len(ga) == 18
         for k in ga:
             assert torch.equal(ga[k], gb[k]), k
+
+
+def test_dnet_sliced_train_forward_captured_bitwise(nconv_amd, gpu, monkeypatch):
+    """The batch-sliced training forward and its backward under hipGraph capture (B = 3 at 16 x 16:
+    slices of 1 + 2 frames on two streams, the weight gradients on a third): the output and all 18
+    gradients of three replays equal the eager iteration bitwise -- the side streams outlive the
+    graph, every fork is joined, and what crosses streams is allocated before the fork or handed
+    over (_streams.py)."""
+    D, St = nconv_amd.dnet, nconv_amd._streams
+    forks = []
+    fork_join = St.fork_join
+    monkeypatch.setattr(St, "fork_join", lambda purpose, *a: forks.append(purpose) or fork_join(purpose, *a))
+    monkeypatch.setattr(D, "TRAIN_FWD_STREAMS", 2)
+    g = torch.Generator().manual_seed(43)
+    S = sparse_depth(g, 3, 16, 16, density=0.3).to(gpu)
+    gt = (torch.rand(3, 1, 16, 16, generator=g) * 80).to(gpu)
+    net = make_net(nconv_amd, "generalized", gpu)
+    net.train()
+    params = dict(net.named_parameters())
+    w0 = {k: p.detach().clone() for k, p in params.items()}
+
+    def restore():
+        with torch.no_grad():
+            for k, p in params.items():  # (every training forward drifts the weights: EnforcePos)
+                p.copy_(w0[k])
+
+    def iteration():
+        out = net(S)
+        nconv_amd.train.calculate_loss(out, gt, True).backward()
+        return out
+
+    cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):  # (eager, off the default stream as a capture's warm-up must be)
+        out_e = iteration().detach().clone()
+        grads_e = {k: p.grad.clone() for k, p in params.items() if p.grad is not None}
+    cur.wait_stream(side)
+    assert forks == ["train_fwd"] and len(grads_e) == 18
+    restore()
+    net.zero_grad(set_to_none=True)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out_g = iteration()
+    assert forks == ["train_fwd"] * 2
+    for r in range(3):
+        restore()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out_g.detach(), out_e), r
+        grads_g = {k: p.grad for k, p in params.items() if p.grad is not None}
+        assert set(grads_g) == set(grads_e)
+        for k in grads_e:
+            assert torch.equal(grads_g[k], grads_e[k]), (r, k)
