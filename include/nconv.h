@@ -1231,6 +1231,60 @@ typedef struct nconv_depth_ipbasic {
 int nconv_depth_ipbasic(const struct nconv_depth_ipbasic* d, float* dst, long long dst_image_stride,
                         long long dst_row_stride, float* work_plane, int* work_top, void* stream);
 
+/* Added under ABI 27 (purely additive: one new entry point and one new struct, nothing existing
+ * changes, so NCONV_ABI_VERSION stays 27). The nearest-sample transform of a sparse depth plane: for
+ * every pixel which input sample is nearest and how far away it is, the exact Euclidean distance
+ * transform with its feature map. Nearest-neighbour interpolation (the other non-learned baseline of the
+ * depth-completion tables; it fills every pixel and keeps its input samples bit for bit), the distance
+ * to the nearest sample as a plane (an input channel, a confidence prior, the strata of a
+ * distance-stratified error), and the mask "farther than r pixels from any return". Integer geometry:
+ * no floating-point arithmetic takes part in any decision. For image b of the (B, H, W) view and pixel
+ * p = (r, c):
+ *   validity    a pixel q = (r', c') is a sample iff its value is finite and > floor. floor = -inf makes
+ *               every finite value a sample; NaN, +-inf, and -0.0 / +0.0 under floor = 0 are not samples.
+ *   distance    d2(p, q) = (r - r')^2 + (c - c')^2, an int32: shapes with H^2 + W^2 >= 2^31 are refused.
+ *   nearest     near(p) = the sample of the same image with the smallest d2, ties to the smallest pixel
+ *               number r' * W + c'. A sample is its own nearest (d2 = 0).
+ *   range       with max_dist2 >= 0, a pixel whose nearest sample has d2 > max_dist2 has none;
+ *               max_dist2 < 0: no limit. An image without samples has none anywhere.
+ *   outputs     each optional (NULL: skipped), at least one required:
+ *               dst    fp32 view with its own strides: the source value at near(p), bit for bit;
+ *                      +0.0f where there is none
+ *               index  (B, H, W) int32 contiguous: the pixel number of near(p); -1
+ *               dist2  (B, H, W) int32 contiguous: d2(p, near(p)); 0x7FFFFFFF (so that the mask
+ *                      dist2 <= r^2 is false there)
+ *               dist   (B, H, W) fp32 contiguous: the correctly rounded sqrtf((float)d2); +inf
+ * The result is a function of the input alone: identical on every run. The source is only read.
+ * (the struct tag shares its name with the entry point: spell the type `struct nconv_depth_nearest`
+ * or nconv_depth_nearest_desc) */
+typedef struct nconv_depth_nearest {
+    int B, H, W;
+    const float* src;               /* fp32 view: B planes of H rows of W, 4-byte aligned          */
+    long long src_image_stride;     /* elements; ignored when B == 1                               */
+    long long src_row_stride;       /* elements, >= W                                              */
+    float floor;                    /* a sample is finite and > floor; -inf: every finite value    */
+    int max_dist2;                  /* >= 0: the largest d2 that counts; < 0: no limit             */
+} nconv_depth_nearest_desc;
+
+/* dst: fp32 view of B planes of H rows of W with its own strides in elements; index, dist2, dist:
+ * contiguous (B, H, W) planes; whichever is not NULL is overwritten entirely. work: a contiguous
+ * (B, H, W) int32 plane, required and overwritten (per pixel the row of the nearest sample of its
+ * column, the upper one on a tie, -1 for a column without samples). src, work and the outputs must be
+ * pairwise disjoint: other pixels are read, so there is no in-place operation, and the host compares
+ * the byte extents.
+ * Two kernels on `stream`: a column pass into work (a wave takes 64 rows of 64 columns, their validity
+ * as one 64-bit mask per lane) and a row pass that searches outwards from the pixel's own column for
+ * the smallest key (d2 << 32) | pixel number until the squared column offset exceeds the best d2 or
+ * max_dist2, O(distance to the nearest sample) per pixel and O(W) at worst. No atomics, no host
+ * synchronisation, no allocation, no waiting between workgroups: capturable. No byte outside the source
+ * view's extent is read.
+ * -EINVAL before any launch for a NULL descriptor / src / work, all four outputs NULL, B, H or W <= 0,
+ * B * H * W >= 2^31, H^2 + W^2 >= 2^31, a NaN floor, a pointer that is not 4-byte aligned, a src or dst
+ * view whose strides are smaller than its rows / images or whose image spans 2^31 bytes or more, and
+ * src, work or an output overlapping another of them. */
+int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long long dst_image_stride,
+                        long long dst_row_stride, int* index, int* dist2, float* dist, int* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

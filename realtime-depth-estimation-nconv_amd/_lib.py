@@ -103,6 +103,7 @@ EXPORTED = (
     "nconv_depth_sparsification_workspace_bytes",
     "nconv_depth_sparsification",
     "nconv_depth_ipbasic",
+    "nconv_depth_nearest",
 )
 
 
@@ -258,6 +259,12 @@ class NconvDepthIpbasic(ctypes.Structure):
                 ("keep_samples", ctypes.c_int)]
 
 
+class NconvDepthNearest(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("src", ctypes.c_void_p),
+                ("src_image_stride", ctypes.c_longlong), ("src_row_stride", ctypes.c_longlong),
+                ("floor", ctypes.c_float), ("max_dist2", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -385,6 +392,8 @@ def _declare(lib):
     lib.nconv_depth_sparsification.argtypes = [ctypes.POINTER(NconvDepthSparsification), P, ctypes.c_size_t, P]
     lib.nconv_depth_ipbasic.restype = I
     lib.nconv_depth_ipbasic.argtypes = [ctypes.POINTER(NconvDepthIpbasic), P, L, L, P, P, P]
+    lib.nconv_depth_nearest.restype = I
+    lib.nconv_depth_nearest.argtypes = [ctypes.POINTER(NconvDepthNearest), P, L, L, P, P, P, P, P]
 
 
 def lib():

@@ -1,6 +1,6 @@
 // capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
 // and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment,
-// sparsification curves and the IP-Basic baseline.
+// sparsification curves, the IP-Basic baseline and the nearest-sample transform.
 // Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
 // and calls its launcher (capi_common.h).
 #include "capi_common.h"
@@ -616,6 +616,52 @@ int nconv_depth_ipbasic(const struct nconv_depth_ipbasic* d, float* dst, long lo
     a.keep_samples = d->keep_samples != 0;
     a.dst = dst, a.dbs = dv.bs, a.drs = dv.rs;
     return launched(fn, nconv::launch_depth_ipbasic, a, (hipStream_t)stream);
+}
+
+int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long long dst_image_stride,
+                        long long dst_row_stride, int* index, int* dist2, float* dist, int* work, void* stream) {
+    const char* fn = "nconv_depth_nearest";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->src || !work) return fail(-22, fn, "null src or work");
+    if (!dst && !index && !dist2 && !dist) return fail(-22, fn, "no output at all (dst, index, dist2 or dist)");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return fail(-22, fn, "batch too large: B * H * W must be below 2^31");
+    if ((long long)H * H + (long long)W * W >= (1LL << 31))
+        return fail(-22, fn, "image too large: H^2 + W^2 must be below 2^31 (squared distances are int32)");
+    if (d->floor != d->floor) return fail(-22, fn, "floor is NaN");
+    if ((size_t)d->src % 4 || (size_t)dst % 4 || (size_t)index % 4 || (size_t)dist2 % 4 || (size_t)dist % 4 ||
+        (size_t)work % 4)
+        return fail(-22, fn, "src / dst / index / dist2 / dist / work not 4-byte aligned");
+    nconv::NearestArgs a{};
+    a.B = B, a.H = H, a.W = W;
+    if (const char* why = view_args(d->src, B, H, W, 4, d->src_image_stride, d->src_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.s))
+        return fail(-22, fn, (std::string("src: ") + why).c_str());
+    // src, work and the outputs: the byte extents must be pairwise disjoint (other pixels are read)
+    const long long plane = 4LL * B * H * W;
+    Extent ext[6];
+    int n = 0;
+    ext[n++] = view_extent(d->src, B, H, W, a.s.bs, 0, a.s.rs, 1, 4, "src");
+    ext[n++] = flat_extent(work, plane, "work");
+    if (dst) {
+        nconv::PlaneView dv{};
+        if (const char* why =
+                view_args(dst, B, H, W, 4, dst_image_stride, dst_row_stride, kNoStrideLimit, 16, kViewPoints, dv))
+            return fail(-22, fn, (std::string("dst: ") + why).c_str());
+        a.dst = dst, a.dbs = dv.bs, a.drs = dv.rs;
+        ext[n++] = view_extent(dst, B, H, W, dv.bs, 0, dv.rs, 1, 4, "dst");
+    }
+    if (index) ext[n++] = flat_extent(index, plane, "index");
+    if (dist2) ext[n++] = flat_extent(dist2, plane, "dist2");
+    if (dist) ext[n++] = flat_extent(dist, plane, "dist");
+    for (int i = 1; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (ext[i].overlaps(ext[j]))
+                return fail(-22, fn, (std::string(ext[i].name) + " overlaps " + ext[j].name).c_str());
+    a.floor = d->floor, a.max_dist2 = d->max_dist2;
+    a.index = index, a.dist2 = dist2, a.dist = dist, a.work = work;
+    return launched(fn, nconv::launch_depth_nearest, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

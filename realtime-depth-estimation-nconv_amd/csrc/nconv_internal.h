@@ -434,4 +434,19 @@ struct IpbasicArgs {
 };
 int launch_depth_ipbasic(const IpbasicArgs& a, hipStream_t st, const char** why);
 
+// Nearest sample and distance map of a sparse depth plane (nconv_depth_nearest), nearest.hip.
+struct NearestArgs {
+    PlaneView s;              // fp32, strides in elements (wide is not used: single pixels are read)
+    int B, H, W;
+    float floor;
+    int max_dist2;            // < 0: no limit
+    float* dst;               // strides in elements; disjoint from the source; or null
+    long long dbs, drs;
+    int* index;               // (B, H, W) contiguous, or null
+    int* dist2;               // (B, H, W) contiguous, or null
+    float* dist;              // (B, H, W) contiguous, or null
+    int* work;                // (B, H, W) contiguous: the row of each column's nearest sample, -1: none
+};
+int launch_depth_nearest(const NearestArgs& a, hipStream_t st, const char** why);
+
 }  // namespace nconv
