@@ -33,6 +33,8 @@ save_checkpoint = _m.train.save_checkpoint
 DepthMetrics = _m.metrics.DepthMetrics
 depth_metric_sums = _m.metrics.depth_metric_sums
 SparsificationCurves = _m.SparsificationCurves
+confidence_loss = _m.train.confidence_loss
+ConfidenceLoss = _m.train.ConfidenceLoss
 
 
 def save_depth(depth_data, path, cmap=None):
@@ -67,6 +69,22 @@ def get_performance(model, val_loader, device_str, use_gradient_loss):
             depth, gt = data["depth"].to(device), data["gt"].to(device)
             est = model(depth)
             losses.append(calculate_loss(est[0, :, :, :], gt[0, :, :, :], use_gradient_loss).item())
+    return sum(losses) / len(losses)
+
+
+def get_performance_confidence(model, val_loader, device_str, lam):
+    """Mean validation confidence loss (confidence_loss, smooth-L1, beta 1) of a step-1 model on element
+    [0] of each batch, the loop of get_performance on model.forward_with_confidence. Device only: the
+    loss and the confidence output are device kernels."""
+    device = torch.device(device_str)
+    model.to(device)
+    model.eval()
+    with torch.no_grad():
+        losses = []
+        for data in val_loader:
+            depth, gt = data["depth"].to(device), data["gt"].to(device)
+            est, conf = model.forward_with_confidence(depth)
+            losses.append(confidence_loss(est[0, :, :, :], gt[0, :, :, :], conf[0, :, :, :], lam).item())
     return sum(losses) / len(losses)
 
 

@@ -301,7 +301,8 @@ typedef struct nconv_bwd_io {
     /* optional: the backward of the 1x1 layer that consumes L's outputs, fused into L's (DNET
      * training: nconv7, 8 -> 1, 1x1, padding 2, after nconv6). tail = nconv7's descriptor; tail_y,
      * tail_cout, tail_gy its outputs and their gradient, (B, 1, Ho + 4, Wo + 4); its cout gradient
-     * is taken as 0 (DNET discards nconv7's confidence). L's gy / gcout are then formed in-kernel
+     * is taken as 0 by nconv_bwd_ex (DNET without a confidence loss discards nconv7's confidence) and
+     * is the extra plane of nconv_bwd_tail_conf below. L's gy / gcout are then formed in-kernel
      * from them (gy, gcout above are ignored and may be NULL), so nconv7's input gradient never
      * reaches HBM; nconv7's weight gradient goes to tail_gw (tail_workspace of
      * nconv_bwd_tail_workspace_bytes(L) bytes; with NCONV_BWD_DEFER_REDUCE tail_nparts partial rows
@@ -333,6 +334,15 @@ int nconv_bwd_ex(const nconv_layer* L, nconv_bwd_io* io, void* workspace, size_t
                  unsigned flags, void* stream);
 size_t nconv_bwd_head_workspace_bytes(const nconv_layer* L);
 size_t nconv_bwd_tail_workspace_bytes(const nconv_layer* L);
+/* nconv_bwd_ex with the fused tail's cout gradient (a new entry point: nconv_bwd_io is unchanged, so
+ * NCONV_ABI_VERSION stays 27). tail_gcout: the gradient of io->tail_cout, the same extent and crop
+ * window as io->tail_gy (0 outside the window); NULL: exactly nconv_bwd_ex. With it nconv7's
+ * {gN, gD} take gcout as the general layer backward does (gD += gcout / s), and nconv7's weight
+ * gradient gains its normaliser term -(sum gcout * cout) / s, summed over nconv7's grid in a fixed
+ * order. -EINVAL where tail_gcout is given without io->tail; -EOPNOTSUPP where L is not the fused
+ * tail's exact-fp32 geometry (as nconv_bwd_ex with io->tail). */
+int nconv_bwd_tail_conf(const nconv_layer* L, nconv_bwd_io* io, const float* tail_gcout, void* workspace,
+                        size_t workspace_bytes, unsigned flags, void* stream);
 
 /* Weight / bias gradients of n (1..16) layers whose nconv_bwd ran with NCONV_BWD_DEFER_REDUCE:
  * layers[k] the descriptor of that call (its weight normaliser wsum is read), workspaces[k] and
@@ -517,6 +527,45 @@ int nconv_depth_loss_fwd(const float* r, long long r_image_stride, long long r_r
 int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* t,
                          long long t_image_stride, long long t_row_stride, int B, int H, int W, int use_gradient_loss,
                          const float* gloss, const void* workspace, size_t workspace_bytes, float* g, void* stream);
+
+/* Confidence loss (new entry points only: no existing struct or signature changes, so
+ * NCONV_ABI_VERSION stays 27). The loss the NConv authors train the output confidence with (Eldesokey,
+ * Felsberg, Khan, TPAMI 2019; ConfLossDecay in their code) on B (H, W) planes of the prediction r, the
+ * output confidence c and the target t, all fp32 with image / row strides in elements (r and c may be
+ * cropped views). The rule, operation by operation in fp32, no contraction:
+ *     v    = (t != 0)
+ *     d    = r - t
+ *     a    = |d|
+ *     NCONV_CONF_LOSS_SMOOTH_L1 (beta > 0):
+ *         e  = a < beta ? ((0.5f * a) * a) / beta : a - 0.5f * beta
+ *         de = a < beta ? d / beta : (d > 0 ? 1 : -1)
+ *     NCONV_CONF_LOSS_L2:
+ *         e  = d * d
+ *         de = 2 * d
+ *     term = v ? e - (lam * c) * (1.0f - e) : 0      (the published err - lam (c v - err c v), lam = 1 / p)
+ *     L    = (sum term) / n, n = B * H * W: the mean over all pixels, as published
+ *     k    = gloss * (1.0f / (float)n)                (gloss NULL: 1)
+ *     g_r  = v ? (k * de) * (1.0f + lam * c) : 0
+ *     g_c  = v ? -((k * lam) * (1.0f - e)) : 0
+ * lam is read from a device fp32 scalar when the kernels run, so a captured training step decays it
+ * without another capture. nconv_conf_loss_fwd writes L to loss[0] (device): fp32 partials over fixed
+ * 16 x 64 tiles (1024 terms each), tiles and images combined in double in a fixed order, no atomics.
+ * nconv_conf_loss_bwd OVERWRITES g_r and g_c (contiguous B x H x W; either may be NULL: skipped); it
+ * reads no workspace. The checks are nconv_depth_loss_*'s, the 2^31-byte extent limit ("plane too
+ * large") included; also -EINVAL: beta <= 0 or NaN, an err_kind outside the enum, null lam. */
+enum nconv_conf_loss_err {
+    NCONV_CONF_LOSS_SMOOTH_L1 = 0,
+    NCONV_CONF_LOSS_L2 = 1
+};
+size_t nconv_conf_loss_workspace_bytes(int B, int H, int W);
+int nconv_conf_loss_fwd(const float* r, long long r_image_stride, long long r_row_stride, const float* c,
+                        long long c_image_stride, long long c_row_stride, const float* t, long long t_image_stride,
+                        long long t_row_stride, int B, int H, int W, int err_kind, float beta, const float* lam,
+                        float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int nconv_conf_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* c,
+                        long long c_image_stride, long long c_row_stride, const float* t, long long t_image_stride,
+                        long long t_row_stride, int B, int H, int W, int err_kind, float beta, const float* lam,
+                        const float* gloss, float* g_r, float* g_c, void* stream);
 
 /* Depth-completion evaluation figures on B (H, W) planes, as twelve raw sums per image. The
  * reference reports only its validation loss (utils.py:18-40); the KITTI (MAE, RMSE, iMAE, iRMSE)

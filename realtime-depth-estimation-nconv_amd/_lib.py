@@ -65,6 +65,7 @@ EXPORTED = (
     "nconv_bwd_ex",
     "nconv_bwd_head_workspace_bytes",
     "nconv_bwd_tail_workspace_bytes",
+    "nconv_bwd_tail_conf",
     "nconv_wgrad_reduce",
     "nconv_wgrad_reduce_ex",
     "nconv_sum_workspace_bytes",
@@ -83,6 +84,9 @@ EXPORTED = (
     "nconv_depth_loss_workspace_bytes",
     "nconv_depth_loss_fwd",
     "nconv_depth_loss_bwd",
+    "nconv_conf_loss_workspace_bytes",
+    "nconv_conf_loss_fwd",
+    "nconv_conf_loss_bwd",
     "nconv_depth_metrics_workspace_bytes",
     "nconv_depth_metrics",
     "nconv_frame_ingest",
@@ -308,6 +312,9 @@ def _declare(lib):
     lib.nconv_bwd_head_workspace_bytes.argtypes = [ctypes.POINTER(NconvLayer)]
     lib.nconv_bwd_tail_workspace_bytes.restype = ctypes.c_size_t
     lib.nconv_bwd_tail_workspace_bytes.argtypes = [ctypes.POINTER(NconvLayer)]
+    lib.nconv_bwd_tail_conf.restype = ctypes.c_int
+    lib.nconv_bwd_tail_conf.argtypes = [ctypes.POINTER(NconvLayer), ctypes.POINTER(NconvBwdIo), P, P, ctypes.c_size_t,
+                                        ctypes.c_uint, P]
     lib.nconv_wgrad_reduce.restype = ctypes.c_int
     lib.nconv_wgrad_reduce.argtypes = [ctypes.c_int, ctypes.POINTER(NconvLayer), P, P, P, P, P]
     lib.nconv_wgrad_reduce_ex.restype = ctypes.c_int
@@ -351,6 +358,12 @@ def _declare(lib):
     lib.nconv_depth_loss_bwd.restype = I
     lib.nconv_depth_loss_bwd.argtypes = [P, L, L, P, L, L, I, I, I, I, P, P, ctypes.c_size_t, P, P]
     F = ctypes.c_float
+    lib.nconv_conf_loss_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_conf_loss_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_conf_loss_fwd.restype = I
+    lib.nconv_conf_loss_fwd.argtypes = [P, L, L, P, L, L, P, L, L, I, I, I, I, F, P, P, P, ctypes.c_size_t, P]
+    lib.nconv_conf_loss_bwd.restype = I
+    lib.nconv_conf_loss_bwd.argtypes = [P, L, L, P, L, L, P, L, L, I, I, I, I, F, P, P, P, P, P]
     lib.nconv_depth_metrics_workspace_bytes.restype = ctypes.c_size_t
     lib.nconv_depth_metrics_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_depth_metrics.restype = I

@@ -53,6 +53,57 @@ int nconv_depth_loss_bwd(const float* r, long long r_image_stride, long long r_r
                     (hipStream_t)stream);
 }
 
+size_t nconv_conf_loss_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 30)) return 0;
+    return nconv::conf_loss_workspace_bytes(B, H, W);
+}
+
+// The operands of nconv_conf_loss_fwd / _bwd checked and turned into the kernels' arguments.
+static const char* conf_loss_args(const float* r, long long rbs, long long rrs, const float* c, long long cbs,
+                                  long long crs, const float* t, long long tbs, long long trs, int B, int H, int W,
+                                  int kind, float beta, const float* lam, nconv::ConfLossArgs& a) {
+    if (!r || !c || !t) return "null plane";
+    if (!lam) return "null lam";
+    if (B <= 0 || H <= 0 || W <= 0) return "non-positive B/H/W";
+    if ((long long)B * H * W > (1LL << 30)) return "batch too large";
+    if (kind != NCONV_CONF_LOSS_SMOOTH_L1 && kind != NCONV_CONF_LOSS_L2) return "unknown err_kind (enum nconv_conf_loss_err)";
+    if (!(beta > 0.f)) return "beta must be positive";
+    a.B = B, a.H = H, a.W = W, a.kind = kind, a.beta = beta, a.lam = lam;
+    if (const char* why = view_args(r, B, H, W, 4, rbs, rrs, kNoStrideLimit, 16, kViewHW, a.r)) return why;
+    if (const char* why = view_args(c, B, H, W, 4, cbs, crs, kNoStrideLimit, 16, kViewHW, a.c)) return why;
+    if (const char* why = view_args(t, B, H, W, 4, tbs, trs, kNoStrideLimit, 16, kViewHW, a.t)) return why;
+    return nullptr;
+}
+
+int nconv_conf_loss_fwd(const float* r, long long r_image_stride, long long r_row_stride, const float* c,
+                        long long c_image_stride, long long c_row_stride, const float* t, long long t_image_stride,
+                        long long t_row_stride, int B, int H, int W, int err_kind, float beta, const float* lam,
+                        float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_conf_loss_fwd";
+    nconv::ConfLossArgs a;
+    if (const char* why = conf_loss_args(r, r_image_stride, r_row_stride, c, c_image_stride, c_row_stride, t,
+                                         t_image_stride, t_row_stride, B, H, W, err_kind, beta, lam, a))
+        return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    if (!workspace || workspace_bytes < nconv::conf_loss_workspace_bytes(B, H, W))
+        return fail(-22, fn, "workspace too small");
+    if ((size_t)workspace % 8) return fail(-22, fn, "workspace not 8-byte aligned");
+    return launched(fn, nconv::launch_conf_loss_fwd, a, loss, workspace, (hipStream_t)stream);
+}
+
+int nconv_conf_loss_bwd(const float* r, long long r_image_stride, long long r_row_stride, const float* c,
+                        long long c_image_stride, long long c_row_stride, const float* t, long long t_image_stride,
+                        long long t_row_stride, int B, int H, int W, int err_kind, float beta, const float* lam,
+                        const float* gloss, float* g_r, float* g_c, void* stream) {
+    const char* fn = "nconv_conf_loss_bwd";
+    nconv::ConfLossArgs a;
+    if (const char* why = conf_loss_args(r, r_image_stride, r_row_stride, c, c_image_stride, c_row_stride, t,
+                                         t_image_stride, t_row_stride, B, H, W, err_kind, beta, lam, a))
+        return fail(-22, fn, why);
+    if (!g_r && !g_c) return fail(-22, fn, "null g_r and g_c");
+    return launched(fn, nconv::launch_conf_loss_bwd, a, gloss, g_r, g_c, (hipStream_t)stream);
+}
+
 size_t nconv_depth_metrics_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > (1LL << 30)) return 0;
     return nconv::metrics_workspace_bytes(B, H, W);

@@ -263,8 +263,14 @@ size_t nconv_bwd_tail_workspace_bytes(const nconv_layer* L) {
 
 int nconv_bwd_ex(const nconv_layer* L, nconv_bwd_io* io, void* workspace, size_t workspace_bytes,
                  unsigned flags, void* stream) {
+    return nconv_bwd_tail_conf(L, io, nullptr, workspace, workspace_bytes, flags, stream);
+}
+
+int nconv_bwd_tail_conf(const nconv_layer* L, nconv_bwd_io* io, const float* tail_gcout, void* workspace,
+                        size_t workspace_bytes, unsigned flags, void* stream) {
     if (const char* why = validate(L, true)) return fail(-22, "nconv_bwd", why);
     if (!io) return fail(-22, "nconv_bwd", "null io");
+    if (tail_gcout && !io->tail) return fail(-22, "nconv_bwd_tail_conf", "tail_gcout without a tail");
     if (!io->y || !io->cout || (!io->gy && !io->tail)) return fail(-22, "nconv_bwd", "null y/cout/gy");
     const LayerDev d = make_dev(L);
     const size_t need = nconv::bwd_workspace_bytes(d);
@@ -330,6 +336,7 @@ int nconv_bwd_ex(const nconv_layer* L, nconv_bwd_io* io, void* workspace, size_t
         a.t7s = T->wsum;
         a.t7eps = T->eps;
         a.t7gy = io->tail_gy;
+        a.t7gco = tail_gcout;
         a.t7y = io->tail_y;
         a.t7co = io->tail_cout;
         a.t7part = (float*)io->tail_workspace;

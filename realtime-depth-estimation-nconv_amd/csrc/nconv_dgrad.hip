@@ -19,8 +19,10 @@ constexpr int kT = 256;
 // gcout = G_c + G_xc * y (nconv7's dgrad_tiled<8,1,1> epilogue, same operations).
 // (t7_off, t7_nd, t7_gy: nconv_internal.h)
 
-template <int OHT, int OWT, int OWP, bool GP = false, bool T7 = false>
+// GC7 (with T7): nconv7's cout gradient is read too (BwdArgs t7gco), one more plane beside its gy.
+template <int OHT, int OWT, int OWP, bool GP = false, bool T7 = false, bool GC7 = false>
 struct GTileStager {
+    static constexpr int N7 = GC7 ? 4 : 3;  // nconv7's gy, y, cout (+ gcout)
     static constexpr int NT = OHT * OWT;
     static constexpr int NE = (NT + 255) / 256;
     static constexpr int PLANE = OHT * OWP;
@@ -49,9 +51,9 @@ struct GTileStager {
         }
     }
 
-    // T7: nconv7's (gy, y, cout) of the elements (loads issued here, {gN7, gD7} formed by t7_form)
+    // T7: nconv7's (gy, y, cout [, gcout]) of the elements (loads issued here, {gN7, gD7} formed by t7_form)
     __device__ __forceinline__ void t7_load(const nconv_layer& L, const BwdArgs& a, int b, int oh0, int ow0, int tid,
-                                            float (&v)[3][NE]) const {
+                                            float (&v)[N7][NE]) const {
         const int pl7 = a.t7ph * a.t7pw;
         const size_t base = (size_t)b * pl7;
         const __amdgpu_buffer_rsrc_t rg = plane_rsrc(a.t7gy + base, pl7 * 4);
@@ -65,12 +67,13 @@ struct GTileStager {
             v[0][k] = ld_f32(rg, off);
             v[1][k] = ld_f32(ry, off);
             v[2][k] = ld_f32(rc, off);
+            if constexpr (GC7) v[N7 - 1][k] = ld_f32(plane_rsrc(a.t7gco + base, pl7 * 4), off);
         }
     }
-    __device__ __forceinline__ void t7_form(const BwdArgs& a, const float (&v)[3][NE]) {
+    __device__ __forceinline__ void t7_form(const BwdArgs& a, const float (&v)[N7][NE]) {
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
-            if constexpr (T7) t7_nd(a, v[0][k], v[1][k], v[2][k], t7n[k], t7d[k]);
+            if constexpr (T7) t7_nd(a, v[0][k], GC7 ? v[N7 - 1][k] : 0.f, v[1][k], v[2][k], t7n[k], t7d[k]);
         }
     }
 
@@ -538,10 +541,14 @@ __global__ __launch_bounds__(kT) void box_weights(const float* __restrict__ w, i
     if (e < 1024) wb[e] = box_weight(w, first_up, e);
 }
 
-template <int MODE, bool T7 = false>
+// The fused tail comes in two forms: T7 (nconv7's cout gradient is 0: nconv_bwd_ex) and T7C (it is
+// read from BwdArgs t7gco: nconv_bwd_tail_conf), one or the other; TAIL below is either.
+template <int MODE, bool T7 = false, bool T7C = false>
 __global__ __launch_bounds__(kT) void dgrad_phase(LayerDev d, BwdArgs a, const float* __restrict__ wbox) {
+    static_assert(!(T7 && T7C), "one form of the fused tail");
+    constexpr bool TAIL = T7 || T7C;
     using C = DgCfg<16, 3>;
-    using GS = GTileStager<C::OHT, C::OWT, C::OWP, false, T7>;
+    using GS = GTileStager<C::OHT, C::OWT, C::OWP, false, TAIL, T7C>;
     constexpr int P = C::P, K = 3, CS = 8;
     constexpr int SK0 = (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST) ? 0 : 8;  // first skip channel of W
     static_assert(C::TH % 2 == 0 && C::TW % 2 == 0 && C::OHT >= C::TH + 2 && C::OWT >= C::TW + 2, "low tile");
@@ -612,8 +619,8 @@ __global__ __launch_bounds__(kT) void dgrad_phase(LayerDev d, BwdArgs a, const f
     // VGPRs, six waves per SIMD instead of four; the tail's input gradient 235 -> 200 us alone
     // (profiles/r5_ab_dgrad_phase_one_ahead.log)
     float va[4][GS::NE];
-    if constexpr (T7) {
-        float v7[3][GS::NE];
+    if constexpr (TAIL) {
+        float v7[GS::N7][GS::NE];
         gs.t7_load(L, a, b, oh0, ow0, tid, v7);
         gs.load(L, a, b, 0, va);
         gs.t7_form(a, v7);
@@ -623,7 +630,7 @@ __global__ __launch_bounds__(kT) void dgrad_phase(LayerDev d, BwdArgs a, const f
 #pragma unroll 1
     for (int o = 0; o < 8; ++o) {
         const int bufi = o & 1;
-        gs.store(L, o, va, tile + bufi * GS::PLANE_STRIDE, T7 ? a.t7w[o] : 0.f);
+        gs.store(L, o, va, tile + bufi * GS::PLANE_STRIDE, TAIL ? a.t7w[o] : 0.f);
         __syncthreads();
         gs.load(L, a, b, o + 1 < 8 ? o + 1 : 7, va);
         fma_plane(o, bufi);
@@ -783,6 +790,11 @@ int go_dgrad(const LayerDev& d, const BwdArgs& a, float* tx, float* tc, hipStrea
                                    MODE == NCONV_LOAD_UPCAT_SKIP_FIRST ? 8 : 0, tx);
                 wb = tx;
             }
+            if constexpr (T7)
+                if (a.t7gco) {
+                    hipLaunchKernelGGL((dgrad_phase<MODE, false, true>), g, dim3(kT), 0, st, d, a, wb);
+                    return 0;
+                }
             hipLaunchKernelGGL((dgrad_phase<MODE, T7>), g, dim3(kT), 0, st, d, a, wb);
         } else {
             hipLaunchKernelGGL((dgrad_tiled<CIN, COUT, K, MODE>), g, dim3(kT), 0, st, d, a, tx, tc);

@@ -75,11 +75,14 @@ struct BwdArgs {
     int* t7nparts;
     int t7ph, t7pw, t7pc0;  // nconv7's planes: (t7ph, t7pw) holding its grid from row / column t7pc0
     const float* box;  // optional precomputed box weights of an exactly-2x UPCAT layer (dgrad_phase)
+    // nconv7's cout gradient (nconv_bwd_tail_conf), the same planes as t7gy; null: 0. Last, so that the
+    // kernel-argument offsets of the fields above stay as they were.
+    const float* t7gco;
 };
 // nconv7 (1x1, padding 2) consumer fused into its producer's backward (T7): byte offset of nconv6
 // pixel (oh, ow) in nconv7's planes -- its (Ho + 4) x (Wo + 4) grid, or the window of it that DNET's
 // crop keeps (t7ph x t7pw from row / column t7pc0) -- or oob outside nconv6's grid or the window (a
-// zero gradient there); nconv7's {gN7, gD7} from its (gy, y, cout) (its cout gradient is 0);
+// zero gradient there); nconv7's {gN7, gD7} from its (gy, gcout, y, cout) (gcout: 0 without t7gco);
 // nconv6's (gy, gcout) from them and w7[o] as nconv7's own 1x1 input gradient forms them
 // (dgrad_tiled<8,1,1>'s epilogue, same operations)
 __device__ __forceinline__ unsigned t7_off(const BwdArgs& a, int oh, int ow, int Ho, int Wo, unsigned oob) {
@@ -89,8 +92,9 @@ __device__ __forceinline__ unsigned t7_off(const BwdArgs& a, int oh, int ow, int
                ? (unsigned)(r * a.t7pw + c) * 4u
                : oob;
 }
-__device__ __forceinline__ void t7_nd(const BwdArgs& a, float gy9, float y9, float co9, float& gN7, float& gD7) {
-    nconv_grad_nd(gy9, 0.f, y9, co9, a.t7eps, a.t7b[0], a.t7s[0], gN7, gD7);
+__device__ __forceinline__ void t7_nd(const BwdArgs& a, float gy9, float gco9, float y9, float co9, float& gN7,
+                                      float& gD7) {
+    nconv_grad_nd(gy9, gco9, y9, co9, a.t7eps, a.t7b[0], a.t7s[0], gN7, gD7);
 }
 __device__ __forceinline__ void t7_gy(float w7, float gN7, float gD7, float y, float co, float& gy, float& gco) {
     const float gxc = fmaf(w7, gN7, 0.f), gc = fmaf(w7, gD7, 0.f);  // the 1x1 dgrad's accumulators
@@ -237,6 +241,20 @@ size_t loss_workspace_bytes(int B, int H, int W);
 int launch_loss_fwd(const LossArgs& a, int grad_loss, float* loss, float* ws, hipStream_t st, const char** why);
 int launch_loss_bwd(const LossArgs& a, int grad_loss, const float* gout, const float* ws, float* g, hipStream_t st,
                     const char** why);
+
+// Confidence loss (nconv_conf_loss_fwd / _bwd, conf_loss.hip) on B planes.
+struct ConfLossArgs {
+    PlaneView r, c, t;  // prediction, confidence, target: fp32, strides in elements; wide: 16-byte aligned
+                        // base and strides, four pixels of a row then come in one load (plane_io.h)
+    int B, H, W;
+    int kind;           // enum nconv_conf_loss_err
+    float beta;
+    const float* lam;   // device scalar
+};
+size_t conf_loss_workspace_bytes(int B, int H, int W);
+int launch_conf_loss_fwd(const ConfLossArgs& a, float* loss, void* ws, hipStream_t st, const char** why);
+int launch_conf_loss_bwd(const ConfLossArgs& a, const float* gloss, float* g_r, float* g_c, hipStream_t st,
+                         const char** why);
 
 // Evaluation metrics (the twelve raw sums of nconv_depth_metrics) on B planes.
 struct MetricsArgs {

@@ -75,9 +75,12 @@ constexpr int kWmStoreStep = 1;  // after which k-step the next row's staging is
 // {gN, gD} (GP: pooled gradients routed in; T7: gy / gcout from nconv7's planes), writes channel o
 // to row + o * PITCH (gD gpart floats on) and adds the strip's own columns (lanes >= K-1 and the
 // halo) to the bias / normaliser sums that finish() reduces. A row that is not valid
-// (wgrad_mfma2's padding of an odd last row) loads and stores zeros.
-template <int COUT, int K, int PITCH, bool GP, bool T7>
+// (wgrad_mfma2's padding of an odd last row) loads and stores zeros. GC7 (with T7): nconv7's cout
+// gradient (BwdArgs t7gco) is read beside its gy, and the strip's sum of gcout * cout over its own
+// pixels goes to nconv7's partial row (its normaliser term, applied by wgrad_finish).
+template <int COUT, int K, int PITCH, bool GP, bool T7, bool GC7 = false>
 struct GRowStager {
+    static constexpr int N7 = GC7 ? 4 : 3;
     static constexpr int OPW = COUT / 4;
     static constexpr int NG = GP ? 7 : 4;  // gy, gco, y, cout (+ pooled gy, gcout, argmax code)
     static constexpr int NH = OPW * (K - 1);
@@ -87,7 +90,8 @@ struct GRowStager {
     bool hl;
     int hkk, hcol, ho;
     float gq[OPW][NG], gh[NG];
-    float g7[T7 ? 2 : 1][3];                           // nconv7's gy, y, cout (T7): main, halo
+    float g7[T7 ? 2 : 1][N7];                          // nconv7's gy, y, cout [, gcout] (T7): main, halo
+    float gs7[1];                                      // nconv7's sum gcout * cout (GC7)
     float w7n[T7 ? OPW : 1], w7d[T7 ? OPW : 1];        // nconv7's weight-gradient sums
     float w7nh, w7dh;
     float gb_acc[OPW], gs_acc[OPW], gb_h, gs_h;
@@ -100,7 +104,7 @@ struct GRowStager {
         plane = L.Ho * L.Wo, pplane = (L.Ho >> 1) * (L.Wo >> 1);
         hl = lane < NH;
         hkk = hl ? lane / (K - 1) : 0, hcol = 64 + lane % (K - 1), ho = w + 4 * hkk;
-        w7nh = w7dh = gb_h = gs_h = 0.f;
+        w7nh = w7dh = gb_h = gs_h = gs7[0] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < OPW; ++kk) {
             gb_acc[kk] = gs_acc[kk] = 0.f;
@@ -132,6 +136,11 @@ struct GRowStager {
             g7[1][0] = ld_f32(r7g, o1);
             g7[1][1] = ld_f32(r7y, o1);
             g7[1][2] = ld_f32(r7c, o1);
+            if constexpr (GC7) {
+                const __amdgpu_buffer_rsrc_t r7q = plane_rsrc(a.t7gco + base7, pl7 * 4);
+                g7[0][N7 - 1] = ld_f32(r7q, o0);
+                g7[1][N7 - 1] = ld_f32(r7q, o1);
+            }
         }
         const size_t base = (size_t)b * COUT * plane;
         const int bytes = COUT * plane * 4;
@@ -196,7 +205,17 @@ struct GRowStager {
         float n7[2] = {0.f, 0.f}, d7[2] = {0.f, 0.f};
         if constexpr (T7)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) t7_nd(a, g7[p][0], g7[p][1], g7[p][2], n7[p], d7[p]);
+            for (int p = 0; p < 2; ++p)
+                t7_nd(a, g7[p][0], GC7 ? g7[p][N7 - 1] : 0.f, g7[p][1], g7[p][2], n7[p], d7[p]);
+        // GC7: each of the strip's own pixels once -- the main columns, the halo lanes of channel slot 0.
+        // INVARIANT: nconv7's planes have one channel, so every wave's g7 holds the same pixels of this row
+        // (load() indexes them by lane alone, not by the wave's channels); each wave therefore carries the
+        // same sum and finish() writes wave 0's. Staging g7 per wave would need a sum over the waves there.
+        // (Guarding this with the wave index instead costs a live SGPR across the row loop: see finish().)
+        if constexpr (GC7) {
+            if (lane >= K - 1) gs7[0] = fmaf(g7[0][N7 - 1], g7[0][2], gs7[0]);
+            if (hl && hkk == 0) gs7[0] = fmaf(g7[1][N7 - 1], g7[1][2], gs7[0]);
+        }
         // the 2x2 window slot of the main / halo column (pooled-gradient routing)
         const unsigned sub = (unsigned)((oh_cur & 1) << 1), ow_m = (unsigned)(ow0 - (K - 1) + lane);
         const unsigned ow_h = (unsigned)(ow0 - (K - 1) + hcol);
@@ -244,7 +263,7 @@ struct GRowStager {
 
     // the wave's channels' sums (the halo lanes' added before the butterfly) -> sums[o] = sum gy,
     // sums[COUT + o] = sum gcout*cout; T7: nconv7's partial row -- 8 weights, then its (unused) sum
-    // gy / sum gcout*cout slots
+    // gy slot and its sum gcout*cout (0 without GC7)
     __device__ __forceinline__ void finish(const BwdArgs& a, float* sums) const {
         // (the wave index read afresh: held from init() it is spilled across the row loop)
         const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -275,21 +294,31 @@ struct GRowStager {
                 }
                 if (lane == 0) o7[w + 4 * kk] = sn + sd;
             }
-            if (threadIdx.x < 2) o7[8 + threadIdx.x] = 0.f;
+            if constexpr (GC7) {  // wave 0's sum: all four waves hold the same one (store()'s invariant)
+                float sg = gs7[0];
+#pragma unroll
+                for (int sh = 32; sh > 0; sh >>= 1) sg += __shfl_xor(sg, sh);
+                if (threadIdx.x == 0) o7[8] = 0.f, o7[9] = sg;
+            } else {
+                if (threadIdx.x < 2) o7[8 + threadIdx.x] = 0.f;
+            }
         }
     }
 };
 
 // wgrad_mfma: the 16 -> 8 3x3 UpCat layers, with and without the fused nconv7 backward (T7); the
 // 8 -> 8 5x5 layers take wgrad_mfma2 below.
-template <int CIN, int COUT, int K, int MODE, bool T7 = false>
+// The fused tail comes in two forms, as in dgrad_phase: T7 (nconv7's cout gradient is 0) and T7C (it
+// is read from BwdArgs t7gco), one or the other.
+template <int CIN, int COUT, int K, int MODE, bool T7 = false, bool T7C = false>
 __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(kWmWaves, 8))) void wgrad_mfma(
     LayerDev d, BwdArgs a, float* part, int nstrip, int nseg, int seg_rows) {
+    static_assert(!(T7 && T7C), "one form of the fused tail");
     static_assert(CIN == 16 && COUT == 8 && K == 3 &&
                       (MODE == NCONV_LOAD_UPCAT_SKIP_FIRST || MODE == NCONV_LOAD_UPCAT_UP_FIRST),
                   "wgrad_mfma: the 16 -> 8 3x3 upsample-concat layers");
     using C = WmCfg<CIN, COUT, K>;
-    using GS = GRowStager<COUT, K, C::GP, false, T7>;
+    using GS = GRowStager<COUT, K, C::GP, false, T7 || T7C, T7C>;
     __shared__ __attribute__((aligned(16))) float lds[C::LDS];
     const nconv_layer& L = d.L;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -718,6 +747,8 @@ int go_wgrad_mfma(const LayerDev& d, const BwdArgs& a, float* part, hipStream_t 
         return launch_wm(wgrad_mfma2<CIN, COUT, K, MODE, GP>, kMfmaRounds, d, a, part, st);
     } else {
         static_assert(!GP, "pooled-gradient routing: the 8 -> 8 5x5 layers");
+        if constexpr (T7)
+            if (a.t7gco) return launch_wm(wgrad_mfma<CIN, COUT, K, MODE, false, true>, kMfmaT7Rounds, d, a, part, st);
         return launch_wm(wgrad_mfma<CIN, COUT, K, MODE, T7>, T7 ? kMfmaT7Rounds : kMfmaRounds, d, a, part, st);
     }
 }

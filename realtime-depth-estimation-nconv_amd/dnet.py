@@ -175,6 +175,12 @@ class DNETFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, specs, capture, crop, S, *p):
         """p: DNETArgs.flatten()."""
+        return DNETFn._forward(ctx, False, specs, capture, crop, S, *p)
+
+    @staticmethod
+    def _forward(ctx, train_conf, specs, capture, crop, S, *p):
+        """train_conf: the output confidence is differentiable too (DNETConfFn); False leaves the
+        graph, its saved tensors and its launches as DNET.forward builds them."""
         W, wph, w21, ctx.wbox = DNETArgs.unflatten(p)
         sp = specs
         pooled = _materialise_pool(S)
@@ -207,8 +213,9 @@ class DNETFn(torch.autograd.Function):
         ctx.pooled = pooled
         ctx.save_for_backward(S, *p[:27], *acts)
         x9, c9 = acts[16], acts[17]
-        ctx.mark_non_differentiable(c9)
-        ctx.set_materialize_grads(False)  # no zero-filled gradient for the never-used c9
+        if not train_conf:
+            ctx.mark_non_differentiable(c9)
+        ctx.set_materialize_grads(False)  # no zero-filled gradient for a c9 (or x9) that is never used
         return x9, c9
 
     @staticmethod
@@ -219,6 +226,8 @@ class DNETFn(torch.autograd.Function):
         X = [None] + [(acts[2 * i], acts[2 * i + 1]) for i in range(9)]  # X[k] = output of layer k
         if g9 is None:  # (grads are not materialised)
             g9 = torch.zeros_like(X[9][0])
+        if gc9 is not None:  # (DNETConfFn only; the unfused branch hands it to nconv7's general backward)
+            gc9 = gc9.contiguous()
         wbox = (None, None, None) if ctx.wbox is None else tuple(ctx.wbox)
         need_S, *need = ctx.needs_input_grad[3:]  # (after specs, capture, crop: S, then w1, b1, s1, w2, ...)
         gw = [torch.empty_like(W[i][0]) if need[3 * i] else None for i in range(9)]
@@ -247,14 +256,15 @@ class DNETFn(torch.autograd.Function):
         def bwd(k, a, b, ga, gb_, acc=False, src_a=None, spec=None, pool_grad=None, box=None):
             xa, ca = src_a if src_a is not None else (X[a] if a else (S, None))
             xb, cb = X[b] if b else (None, None)
-            gy, gco = G[k] if G[k] is not None else (g9, None)
+            gy, gco = G[k] if G[k] is not None else (g9, gc9)
             layer_bwd(spec or sp[k - 1], (xa, ca, xb, cb, *W[k - 1]), X[k][0], X[k][1], gy, gco,
                       (*(ga or (None, None)), *(gb_ or (None, None))), gw[k - 1], gb[k - 1], accumulate=acc,
                       pool_grad=pool_grad, box=box)
 
         G[2], G[7] = (e(X[2][0]), e(X[2][1])), (e(X[7][0]), e(X[7][1]))
-        # (c9 is non-differentiable; nconv7's weight gradient is accumulated inside nconv6's weight-
-        # gradient pass, so the fused form needs nconv6's gw or gb too)
+        # (nconv7's weight gradient is accumulated inside nconv6's weight-gradient pass, so the fused
+        # form needs nconv6's gw or gb too; gc9, the output confidence's gradient, is None unless a
+        # confidence loss was applied to forward_with_confidence's pair)
         if ctx.crop is not None or (FUSE_TAIL_BWD and ctx.pooled and _exact_up(*S.shape[2:]) and gw[8] is not None
                                     and (gw[7] is not None or gb[7] is not None)):
             # nconv7's backward inside nconv6's (nconv_bwd_ex tail): its input gradient never reaches
@@ -265,7 +275,8 @@ class DNETFn(torch.autograd.Function):
             g9c = g9.contiguous()
             layer_bwd(sp[7], (X[2][0], X[2][1], X[7][0], X[7][1], *W[7]), X[8][0], X[8][1], None, None,
                       (*G[2], *G[7]), gw[7], gb[7],
-                      tail=(sp[8], *W[8], X[9][0], X[9][1], g9c, gw[8], None if ctx.crop is None else 1),
+                      tail=(sp[8], *W[8], X[9][0], X[9][1], g9c, gw[8], None if ctx.crop is None else 1,
+                            *(() if gc9 is None else (gc9,))),
                       box=wbox[2])
             if gb[8] is not None:
                 red.add_sum(g9c, gb[8])
@@ -314,6 +325,16 @@ class DNETFn(torch.autograd.Function):
         red.run(S.device)
         grads = itertools.chain.from_iterable((gw[i], gb[i], None) for i in range(9))
         return (None, None, None, gS, *grads, None, None, None)  # (specs, capture, crop, S, layers, wph, w21, wbox)
+
+
+class DNETConfFn(DNETFn):
+    """DNETFn with a differentiable output confidence (DNET.forward_with_confidence under autograd):
+    the same forward launches; the backward takes the confidence's gradient gc9 into nconv7's backward
+    -- the fused tail's extra plane (nconv_bwd_tail_conf) or the general layer backward's gcout."""
+
+    @staticmethod
+    def forward(ctx, specs, capture, crop, S, *p):
+        return DNETFn._forward(ctx, True, specs, capture, crop, S, *p)
 
 
 def _tail_train(sp6, sp7, x2, c2, x7, c7, W6, W7, w6, crop=None, out=None):
@@ -511,15 +532,7 @@ class DNET(nn.Module):
 
         (l1, l2, d1, d2, d3, l4, l5, l6, l7) = layers
         if grad and self.whole_graph_autograd and S.shape[0] > 0:
-            specs = (l1.spec(_lib.THRESH, 0.01), l2.spec(), d1.spec(_lib.POOL2), d2.spec(_lib.POOL2),
-                     d3.spec(_lib.POOL2), l4.spec(_lib.UPCAT_SKIP_FIRST), l5.spec(_lib.UPCAT_SKIP_FIRST),
-                     l6.spec(_lib.UPCAT_UP_FIRST), l7.spec())
-            wsum, wph, w21, wbox = self._train_prologue(layers, S) or \
-                (self._prologue(layers, S), self._phase_weights(S.device), None, None)
-            args = DNETArgs(tuple((m_.weight, m_.bias, s_) for m_, s_ in zip(layers, wsum)), wph, w21, wbox)
-            crop = (out_h, out_w) if self._tail_crop(S, wph) else None
-            xo, _ = DNETFn.apply(specs, self.capture, crop, S, *args.flatten())
-            return xo if crop is not None else CropFn.apply(xo, out_h, out_w)
+            return self._whole_graph(S, layers, DNETFn)[0]
 
         wsum = self._prologue(layers, S)
         (s1, s2, sd1, sd2, sd3, s4, s5, s6, s7) = wsum
@@ -542,15 +555,44 @@ class DNET(nn.Module):
         xo, co = f(l7.spec(), xo, co, None, None, l7.weight, l7.bias, s7)
         return xo[:, :, 1:1 + out_h, 1:1 + out_w]
 
+    def _whole_graph(self, S, layers, fn):
+        """(depth, confidence) of the whole-graph training pass, fn = DNETFn (the confidence is not
+        differentiable: forward drops it) or DNETConfFn; cropped by the fused tail where it can
+        (_tail_crop), else by CropFn, the confidence by the same window."""
+        (l1, l2, d1, d2, d3, l4, l5, l6, l7) = layers
+        out_h, out_w = crop_hw(S.shape[2], S.shape[3], self.crop)
+        specs = (l1.spec(_lib.THRESH, 0.01), l2.spec(), d1.spec(_lib.POOL2), d2.spec(_lib.POOL2),
+                 d3.spec(_lib.POOL2), l4.spec(_lib.UPCAT_SKIP_FIRST), l5.spec(_lib.UPCAT_SKIP_FIRST),
+                 l6.spec(_lib.UPCAT_UP_FIRST), l7.spec())
+        wsum, wph, w21, wbox = self._train_prologue(layers, S) or \
+            (self._prologue(layers, S), self._phase_weights(S.device), None, None)
+        args = DNETArgs(tuple((m_.weight, m_.bias, s_) for m_, s_ in zip(layers, wsum)), wph, w21, wbox)
+        crop = (out_h, out_w) if self._tail_crop(S, wph) else None
+        xo, co = fn.apply(specs, self.capture, crop, S, *args.flatten())
+        if crop is not None:
+            return xo, co
+        return CropFn.apply(xo, out_h, out_w), (CropFn.apply(co, out_h, out_w) if fn is DNETConfFn else None)
+
     def forward_with_confidence(self, S):
         """(depth, confidence), both (B, 1, out_h, out_w): forward(S)'s prediction, bit for bit,
         and the confidence nconv7 propagates beside it (step1.py:92 computes it, :94 drops it),
-        cropped like the depth; 0 where the crop reaches nconv7's zero border. Inference only: it
-        raises where gradients would be recorded, and takes the fused inference path (nconv_fwd_tail
-        writes both), which needs min(H, W) >= 16."""
+        cropped like the depth; 0 where the crop reaches nconv7's zero border.
+
+        Without autograd it takes the fused inference path (nconv_fwd_tail writes both), which needs
+        min(H, W) >= 16. In training mode, where gradients are recorded, it takes forward's
+        whole-graph training pass (the same launches, the same crop path) and both outputs are
+        differentiable: a loss on the confidence (train.ConfidenceLoss) reaches every layer. A model
+        in eval mode that would record gradients, or a CPU input, is refused as before."""
         if self._records_grad(S):
-            raise RuntimeError("DNET.forward_with_confidence is inference only: call it under torch.no_grad() "
-                               "(the output confidence has no backward)")
+            if not (self.training and torch.is_tensor(S) and S.is_cuda):
+                raise RuntimeError("DNET.forward_with_confidence is inference only outside training mode: call it "
+                                   "under torch.no_grad(), or in training mode (train()) on a device input for a "
+                                   "differentiable confidence")
+            S = self._checked_input(S, "DNET.forward_with_confidence")
+            if not self.whole_graph_autograd or S.shape[0] == 0:
+                raise RuntimeError("DNET.forward_with_confidence under autograd needs the whole-graph training pass "
+                                   "(whole_graph_autograd) and a non-empty batch")
+            return self._whole_graph(S, [getattr(self, n) for n in LAYERS], DNETConfFn)
         S = self._checked_input(S, "DNET.forward_with_confidence")
         H, W = S.shape[2], S.shape[3]
         if min(H, W) < 16:

@@ -356,8 +356,9 @@ def layer_backward(spec: LayerSpec, inputs, y, co, gy, gco, gin, gw, gb, accumul
     is fused into this layer's (nconv_bwd_ex tail; gy / gco are then unused and may be None; nconv7's
     bias gradient is the caller's). The input and the weight gradient are separate kernels. tail may
     carry a 9th element, the crop origin of nconv7's planes when they hold a window of its grid
-    (DNET's crop: nconv_bwd_io tail_crop0 / tail_h / tail_w). box: an exactly-2x UPCAT layer's box
-    weights (train_prologue), else built by this call."""
+    (DNET's crop: nconv_bwd_io tail_crop0 / tail_h / tail_w), and a 10th, the gradient of cout9 (same
+    shape as gy9) or None: the call then goes through nconv_bwd_tail_conf. box: an exactly-2x UPCAT layer's box weights
+    (train_prologue), else built by this call."""
     xa, ca, xb, cb, weight, bias, wsum = inputs
     gxa, gca, gxb, gcb = gin
     dev = y.device
@@ -396,8 +397,18 @@ def layer_backward(spec: LayerSpec, inputs, y, co, gy, gco, gin, gw, gb, accumul
         io.tail_y, io.tail_cout, io.tail_gy = ty.data_ptr(), tco.data_ptr(), tgy.contiguous().data_ptr()
         io.tail_workspace, io.tail_workspace_bytes = tws.data_ptr(), tbytes
         io.tail_gw = _lib.ptr(tgw)
-    rc = lib.nconv_bwd_ex(_lib.ctypes.byref(L), _lib.ctypes.byref(io), _lib.ptr(ws), ws_bytes, flags,
-                          _lib.stream_handle(dev))
+    if tail is not None and len(tail) > 9:
+        tgco = tail[9]
+        if tgco is not None:
+            if tgco.shape != tgy.shape:
+                raise ValueError(f"layer_backward: tail gcout {tuple(tgco.shape)} does not match gy "
+                                 f"{tuple(tgy.shape)}")
+            tgco = tgco.contiguous()
+        rc = lib.nconv_bwd_tail_conf(_lib.ctypes.byref(L), _lib.ctypes.byref(io), _lib.ptr(tgco), _lib.ptr(ws),
+                                     ws_bytes, flags, _lib.stream_handle(dev))
+    else:
+        rc = lib.nconv_bwd_ex(_lib.ctypes.byref(L), _lib.ctypes.byref(io), _lib.ptr(ws), ws_bytes, flags,
+                              _lib.stream_handle(dev))
     if defer is not None and rc >= 0:
         defer.add(L, ws, rc, gw, gb)
         if head is not None:

@@ -4,6 +4,8 @@ Cheap elementwise/reduction glue around the NConv path (PyTorch-ROCm ops), excep
   calculate_loss                    utils.py:138-151   masked RMSE*0.8 + Sobel-gradient*0.2 (or MSE);
                                     on device planes / batches the fused libnconv kernels (DepthLossFn)
   gradient_loss / gradient_x / _y   utils.py:95-136
+  confidence_loss / ConfidenceLoss  the NConv authors' confidence loss on (prediction, confidence), fused
+                                    (ConfLossFn); not in the reference, which never trains the confidence
   calculate_loss_multi_resolution   utils.py:63-71     each scale bilinear-resized to 480x640, [0] only
   get_optimizer                     utils.py:53-61     AdamW / SGD / RMSprop
   save_checkpoint / load_state_dict_compat  utils.py:42-51, models/step2.py:29-36
@@ -123,6 +125,117 @@ def calculate_loss(reconstructed_img, target_img, use_gradient_loss):
     return _calculate_loss_torch(reconstructed_img, target_img, use_gradient_loss)
 
 
+CONF_LOSS_ERR = {"smooth_l1": 0, "l2": 1}  # enum nconv_conf_loss_err
+
+
+class ConfLossFn(torch.autograd.Function):
+    """The confidence loss of the NConv authors (Eldesokey et al., TPAMI 2019; ConfLossDecay) as
+    libnconv kernels (nconv_conf_loss_fwd / _bwd: 2 launches forward, 1 backward; the rule is stated
+    in include/nconv.h): L = mean over all pixels of v (e - lam c (1 - e)), v = (t != 0), e the
+    smooth-L1 or squared error of r against t. r, c, t: (H, W), (1, H, W) or (B, 1, H, W) fp32 device
+    planes with unit-stride rows (r and c may be cropped views); lam: a one-element fp32 device
+    tensor, read when the kernels run. Gradients flow to r and c."""
+
+    @staticmethod
+    def forward(ctx, r, c, t, lam, kind, beta):
+        from . import _lib
+        H, W = r.shape[-2], r.shape[-1]
+        B, rbs, rs = _planes(r)
+        _, cbs, cs = _planes(c)
+        _, tbs, ts = _planes(t)
+        lib = _lib.lib()
+        nbytes = lib.nconv_conf_loss_workspace_bytes(B, H, W)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=r.device)
+        loss = torch.empty((), dtype=torch.float32, device=r.device)
+        rc = lib.nconv_conf_loss_fwd(_lib.ptr(r), rbs, rs, _lib.ptr(c), cbs, cs, _lib.ptr(t), tbs, ts, B, H, W,
+                                     kind, beta, _lib.ptr(lam), _lib.ptr(loss), _lib.ptr(ws), nbytes,
+                                     _lib.stream_handle(r.device))
+        _lib.check(rc, "nconv_conf_loss_fwd")
+        ctx.kind, ctx.beta = kind, beta
+        ctx.save_for_backward(r, c, t, lam)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        from . import _lib
+        r, c, t, lam = ctx.saved_tensors
+        H, W = r.shape[-2], r.shape[-1]
+        B, rbs, rs = _planes(r)
+        _, cbs, cs = _planes(c)
+        _, tbs, ts = _planes(t)
+        need_r, need_c = ctx.needs_input_grad[:2]
+        g_r = torch.empty(r.shape, dtype=torch.float32, device=r.device) if need_r else None
+        g_c = torch.empty(c.shape, dtype=torch.float32, device=r.device) if need_c else None
+        if g_r is None and g_c is None:
+            return (None,) * 6
+        gloss = gloss.contiguous()
+        rc = _lib.lib().nconv_conf_loss_bwd(_lib.ptr(r), rbs, rs, _lib.ptr(c), cbs, cs, _lib.ptr(t), tbs, ts, B, H, W,
+                                            ctx.kind, ctx.beta, _lib.ptr(lam), _lib.ptr(gloss), _lib.ptr(g_r),
+                                            _lib.ptr(g_c), _lib.stream_handle(r.device))
+        _lib.check(rc, "nconv_conf_loss_bwd")
+        return g_r, g_c, None, None, None, None
+
+
+def confidence_loss(pred, gt, conf, lam, err="smooth_l1", beta=1.0):
+    """The confidence loss on device planes (ConfLossFn): mean over ALL pixels of
+    v (e - lam conf (1 - e)), v = (gt != 0), e = smooth_l1(pred, gt; beta) or (pred - gt)^2
+    (err="l2"). It rewards confidence where e < 1 and punishes it where e > 1; lam = 1 / p weighs
+    that against the error term (the authors decay it per epoch). lam: a float (uploaded here) or a
+    one-element fp32 tensor on pred's device, which a captured step reads at replay time. The
+    gradients reach pred and conf (DNET.forward_with_confidence in training mode)."""
+    if err not in CONF_LOSS_ERR:
+        raise ValueError(f"confidence_loss: err must be one of {sorted(CONF_LOSS_ERR)}, got {err!r}")
+    if not float(beta) > 0.0:
+        raise ValueError(f"confidence_loss: beta must be positive, got {beta}")
+    for name, x in (("pred", pred), ("gt", gt), ("conf", conf)):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and _planes(x) is not None):
+            raise ValueError(f"confidence_loss: {name} must be an fp32 device plane (H, W), (1, H, W) or (B, 1, H, W) "
+                             "with unit-stride rows")
+    if not (pred.shape == gt.shape == conf.shape and pred.device == gt.device == conf.device):
+        raise ValueError(f"confidence_loss: pred {tuple(pred.shape)}, gt {tuple(gt.shape)} and conf "
+                         f"{tuple(conf.shape)} must have one shape and one device")
+    if gt.requires_grad:
+        raise ValueError("confidence_loss: gt must not require grad")
+    if torch.is_tensor(lam):
+        if not (lam.is_cuda and lam.device == pred.device and lam.dtype == torch.float32 and lam.numel() == 1):
+            raise ValueError("confidence_loss: a tensor lam must be one fp32 element on pred's device")
+        lam = lam.detach()
+    else:
+        lam = torch.full((1,), float(lam), dtype=torch.float32, device=pred.device)
+    return ConfLossFn.apply(pred, conf, gt, lam, CONF_LOSS_ERR[err], float(beta))
+
+
+class ConfidenceLoss(torch.nn.Module):
+    """confidence_loss with lam = 1 / p held as a device buffer: loss((pred, conf), gt) or
+    loss(pred, conf, gt). set_epoch(p) writes 1 / p into the buffer in place, so a GraphedTrainStep
+    that captured this module takes the new value at its next replay (the authors' ConfLossDecay
+    sets p = epoch)."""
+
+    def __init__(self, p=1.0, err="smooth_l1", beta=1.0):
+        super().__init__()
+        if err not in CONF_LOSS_ERR:
+            raise ValueError(f"ConfidenceLoss: err must be one of {sorted(CONF_LOSS_ERR)}, got {err!r}")
+        if not float(beta) > 0.0 or not float(p) > 0.0:
+            raise ValueError(f"ConfidenceLoss: p and beta must be positive, got p={p}, beta={beta}")
+        self.err, self.beta = err, float(beta)
+        self.register_buffer("lam", torch.full((1,), 1.0 / float(p), dtype=torch.float32))
+
+    def set_epoch(self, p):
+        if not float(p) > 0.0:
+            raise ValueError(f"ConfidenceLoss.set_epoch: p must be positive, got {p}")
+        self.lam.fill_(1.0 / float(p))
+
+    def forward(self, pred, conf_or_gt, gt=None):
+        if gt is None:  # loss((pred, conf), gt)
+            (pred, conf), gt = pred, conf_or_gt
+        else:
+            conf = conf_or_gt
+        if self.lam.device != pred.device:
+            raise ValueError(f"ConfidenceLoss: lam is on {self.lam.device}, the prediction on {pred.device}: move "
+                             "the loss with .to(device)")
+        return confidence_loss(pred, gt, conf, self.lam, self.err, self.beta)
+
+
 def calculate_loss_multi_resolution(reconstructed_img, target_img, use_gradient_loss):
     total = 0.0
     for img in reconstructed_img:
@@ -170,7 +283,9 @@ class GraphedTrainStep:
     the data-parallel gradient all-reduce (DataParallelRCCL.allreduce_grads, if the model has it)
     and the optimizer step — captured once in a hipGraph and replayed per call.
 
-    loss_fn(model, *inputs) -> scalar loss tensor. The optimizer must keep its state on the device
+    loss_fn(model, *inputs) -> scalar loss tensor; what the model returns is the closure's business,
+    so a pair works as a tensor does: lambda m, s, gt: conf_loss(m.forward_with_confidence(s), gt)
+    with a ConfidenceLoss, whose lam buffer the replays read afresh. The optimizer must keep its state on the device
     and update it without host synchronisation (torch AdamW / Adam with capturable=True). Inputs
     are copied into static buffers on every call (pass the same tensors to skip the copy). The
     warm-up iterations needed before capture run on a snapshot: parameters, buffers and optimizer
