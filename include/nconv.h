@@ -1334,6 +1334,108 @@ typedef struct nconv_depth_nearest {
 int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long long dst_image_stride,
                         long long dst_row_stride, int* index, int* dist2, float* dist, int* work, void* stream);
 
+/* Depth-driven view warp and photometric loss (new entry points only: no existing struct or signature
+ * changes, so NCONV_ABI_VERSION stays 27). The self-supervised term of Ma, Cavalheiro and Karaman (ICRA
+ * 2019, "Self-supervised Sparse-to-Dense") and the monodepth family: the predicted depth of the current
+ * (target) view and a known relative pose warp a neighbouring (source) camera frame into the target view,
+ * and the difference to the target frame is penalised, the gradient flowing into the depth. The geometry
+ * is nconv_backproject's point followed by nconv_lidar_project's projection; what is new is the bilinear
+ * sampling and its derivative. Each target pixel owns its four taps, so the gradient with respect to the
+ * depth is a gather: no atomics, the same bits on every run.
+ *
+ * The rule, fp32, one rounding per operation in the order written, no contraction. Per target pixel
+ * (b, i, j) with z = depth[b][i][j]; fx, fy, cx, cy = K[0][0], K[1][1], K[0][2], K[1][2] of image b's
+ * 3 x 3 matrix k (k_image_stride 0: one camera); m the row-major 3 x 4 matrix of image b
+ * (m_image_stride 0: one matrix), K_src . [R | t], which takes the target camera frame to source pixels:
+ *     point       tx = (float)j - cx            ty = (float)i - cy
+ *                 x  = (tx * z) / fx            y  = (ty * z) / fy        (nconv_backproject's point)
+ *                 pvalid = z > z_min && z <= z_max      (z_max == 0: FLT_MAX; comparisons: a NaN is not valid)
+ *     project     dot(r, P) = ((r[0] * x + r[1] * y) + r[2] * z) + r[3]    (nconv_lidar_project's dot)
+ *                 a = dot(m[0], P)   bb = dot(m[1], P)   c = dot(m[2], P)
+ *                 u = a / c          v = bb / c                             (IEEE division)
+ *     valid       pvalid && c > 0 && u >= 0 && u <= (float)(Ws - 1) && v >= 0 && v <= (float)(Hs - 1)
+ *                 && (mask == NULL || mask[b][i][j] != 0)
+ *                 all float comparisons made before any integer conversion
+ *     taps        fu = floorf(u)     j0 = (int)fu   j1 = min(j0 + 1, Ws - 1)   wu = u - fu   w0u = 1.0f - wu
+ *                 fv = floorf(v)     i0 = (int)fv   i1 = min(i0 + 1, Hs - 1)   wv = v - fv   w0v = 1.0f - wv
+ *     per channel ch, a00 = src[b][ch][i0][j0], a01 = [i0][j1], a10 = [i1][j0], a11 = [i1][j1]:
+ *                 top = (w0u * a00) + (wu * a01)
+ *                 bot = (w0u * a10) + (wu * a11)
+ *                 s   = (w0v * top) + (wv * bot)
+ *                 warped[b][ch][i][j] = valid ? s : +0.0f
+ *     derivatives dIu = (w0v * (a01 - a00)) + (wv * (a11 - a10))          dIv = bot - top
+ *                 X   = tx / fx                  Y   = ty / fy
+ *                 a'  = ((m[0][0] * X) + (m[0][1] * Y)) + m[0][2]          likewise b' (row 1) and c' (row 2)
+ *                 du  = (a' - (u * c')) / c      dv  = (b' - (v * c')) / c
+ *                 t[ch]   = g_s[ch] * ((dIu[ch] * du) + (dIv[ch] * dv))
+ *                 g_depth = valid ? (C == 1 ? t[0] : (t[0] + t[1]) + t[2]) : +0.0f
+ *     nconv_view_warp_bwd takes g_s[ch] = g_warped[b][ch][i][j].
+ * The photometric loss on top of the warp, with the target frame tgt (B, C, H, W):
+ *     e[ch] = |s[ch] - tgt[b][ch][i][j]|
+ *     term  = valid ? (C == 1 ? e[0] : (e[0] + e[1]) + e[2]) : 0
+ *     n_v   = the number of valid pixels, an integer counted on the device
+ *     den   = (float)C * (float)max(n_v, 1)
+ *     L     = (sum term) / den
+ *     kk    = gloss * (1.0f / den)            (gloss NULL: 1)
+ *     g_s[ch] = kk * sign(s[ch] - tgt[b][ch][i][j]),  sign(d) = d > 0 ? 1 : d < 0 ? -1 : 0
+ *     and g_depth as above; neither warped nor g_s reaches memory.
+ * The sum: fp32 partials over fixed 16 x 64 tiles (1024 terms each), tiles and images combined in double
+ * in a fixed order, divided by den in double and rounded to fp32 once; the count is exact; no atomics.
+ * nconv_photo_loss_fwd leaves L in loss[0] and n_v in the first int of the workspace (both on the device);
+ * nconv_photo_loss_bwd reads n_v from the same workspace: no host synchronisation.
+ *
+ * NOT offered: a gradient with respect to the source image (a scatter); a gradient with respect to m
+ * (poses are inputs); SSIM; an image pyramid (a caller downsamples and scales k and m themselves); pose
+ * estimation. An invalid pixel loads no tap, a valid one reads taps inside the source plane by the
+ * clamps: no byte outside a view's extent is read.
+ * (the entry points are nconv_view_warp_fwd / _bwd; the descriptor's type is `struct nconv_view_warp`
+ * or nconv_view_warp_desc) */
+typedef struct nconv_view_warp {
+    int B, C;                       /* C = 1 or 3 channels of src (and tgt)                        */
+    int H, W;                       /* the target view: depth, mask, tgt, warped, valid, g_depth   */
+    int Hs, Ws;                     /* the source frame                                            */
+    const float* depth;             /* fp32 view: B planes of H rows of W, 4-byte aligned          */
+    long long depth_image_stride;   /* elements; ignored when B == 1                               */
+    long long depth_row_stride;     /* elements, >= W                                              */
+    const unsigned char* mask;      /* uint8 view (B, H, W), or NULL: every pixel may be valid     */
+    long long mask_image_stride;    /* bytes; ignored when B == 1                                  */
+    long long mask_row_stride;      /* bytes, >= W                                                 */
+    const float* src;               /* fp32 view: B images of C planes of Hs rows of Ws            */
+    long long src_image_stride;     /* elements; ignored when B == 1                               */
+    long long src_channel_stride;   /* elements; ignored when C == 1                               */
+    long long src_row_stride;       /* elements, >= Ws                                             */
+    const float* k;                 /* device: 3 x 3 row-major intrinsics of the target camera     */
+    long long k_image_stride;       /* floats between the matrices of two images; 0: one camera    */
+    const float* m;                 /* device: 3 x 4 row-major K_src . [R | t]                     */
+    long long m_image_stride;       /* floats between the matrices of two images; 0: one matrix    */
+    float z_min, z_max;             /* valid depth: z > z_min && z <= z_max; z_max == 0: FLT_MAX   */
+} nconv_view_warp_desc;
+
+/* warped: (B, C, H, W) fp32 contiguous; valid: (B, H, W) uint8 contiguous, 1 / 0; either may be NULL
+ * (skipped), not both. One launch on `stream`. */
+int nconv_view_warp_fwd(const struct nconv_view_warp* d, float* warped, unsigned char* valid, void* stream);
+/* g_warped: (B, C, H, W) fp32 contiguous; g_depth: (B, H, W) fp32 contiguous, OVERWRITTEN. One launch. */
+int nconv_view_warp_bwd(const struct nconv_view_warp* d, const float* g_warped, float* g_depth, void* stream);
+
+/* The fused loss. tgt: fp32 view of B images of C planes of H rows of W with its own strides in
+ * elements. workspace: nconv_photo_loss_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W
+ * <= 0 or B * H * W >= 2^31); the forward writes it, the backward reads its first int (n_v). loss, gloss:
+ * device scalars (gloss NULL: 1). g_depth: (B, H, W) fp32 contiguous, OVERWRITTEN. Two launches forward,
+ * one backward; no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch, for all four entry points: a NULL descriptor, depth, src, k or m; C outside
+ * {1, 3}; B, H, W, Hs or Ws <= 0; H, W, Hs or Ws above 2^24 (pixel coordinates are exact floats);
+ * B * C * H * W >= 2^31; a negative k or m image stride; z_min < 0 or NaN, z_max < z_min or NaN; a
+ * pointer that is not aligned to its element; a view whose strides are negative or smaller than its
+ * rows / planes / images, or one plane of which spans 2^31 bytes or more ("plane too large"); no output
+ * at all; a NULL tgt, loss or g_depth; a workspace that is NULL, too small or not 8-byte aligned. */
+size_t nconv_photo_loss_workspace_bytes(int B, int H, int W);
+int nconv_photo_loss_fwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                         long long tgt_channel_stride, long long tgt_row_stride, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                         long long tgt_channel_stride, long long tgt_row_stride, const float* gloss,
+                         const void* workspace, size_t workspace_bytes, float* g_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

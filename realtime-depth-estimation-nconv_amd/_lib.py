@@ -108,6 +108,11 @@ EXPORTED = (
     "nconv_depth_sparsification",
     "nconv_depth_ipbasic",
     "nconv_depth_nearest",
+    "nconv_view_warp_fwd",
+    "nconv_view_warp_bwd",
+    "nconv_photo_loss_workspace_bytes",
+    "nconv_photo_loss_fwd",
+    "nconv_photo_loss_bwd",
 )
 
 
@@ -269,6 +274,18 @@ class NconvDepthNearest(ctypes.Structure):
                 ("floor", ctypes.c_float), ("max_dist2", ctypes.c_int)]
 
 
+class NconvViewWarp(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("Hs", ctypes.c_int), ("Ws", ctypes.c_int), ("depth", ctypes.c_void_p),
+                ("depth_image_stride", ctypes.c_longlong), ("depth_row_stride", ctypes.c_longlong),
+                ("mask", ctypes.c_void_p), ("mask_image_stride", ctypes.c_longlong),
+                ("mask_row_stride", ctypes.c_longlong), ("src", ctypes.c_void_p),
+                ("src_image_stride", ctypes.c_longlong), ("src_channel_stride", ctypes.c_longlong),
+                ("src_row_stride", ctypes.c_longlong), ("k", ctypes.c_void_p), ("k_image_stride", ctypes.c_longlong),
+                ("m", ctypes.c_void_p), ("m_image_stride", ctypes.c_longlong), ("z_min", ctypes.c_float),
+                ("z_max", ctypes.c_float)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -407,6 +424,16 @@ def _declare(lib):
     lib.nconv_depth_ipbasic.argtypes = [ctypes.POINTER(NconvDepthIpbasic), P, L, L, P, P, P]
     lib.nconv_depth_nearest.restype = I
     lib.nconv_depth_nearest.argtypes = [ctypes.POINTER(NconvDepthNearest), P, L, L, P, P, P, P, P]
+    lib.nconv_view_warp_fwd.restype = I
+    lib.nconv_view_warp_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, P]
+    lib.nconv_view_warp_bwd.restype = I
+    lib.nconv_view_warp_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, P]
+    lib.nconv_photo_loss_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_photo_loss_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_photo_loss_fwd.restype = I
+    lib.nconv_photo_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P]
+    lib.nconv_photo_loss_bwd.restype = I
+    lib.nconv_photo_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P, P]
 
 
 def lib():

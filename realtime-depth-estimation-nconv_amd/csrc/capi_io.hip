@@ -1,6 +1,7 @@
 // capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
 // and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment,
-// sparsification curves, the IP-Basic baseline and the nearest-sample transform.
+// sparsification curves, the IP-Basic baseline, the nearest-sample transform, and the view warp with its
+// photometric loss.
 // Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
 // and calls its launcher (capi_common.h).
 #include "capi_common.h"
@@ -713,6 +714,125 @@ int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long lo
     a.floor = d->floor, a.max_dist2 = d->max_dist2;
     a.index = index, a.dist2 = dist2, a.dist = dist, a.work = work;
     return launched(fn, nconv::launch_depth_nearest, a, (hipStream_t)stream);
+}
+
+// A view of B images of C planes of H rows of W fp32 (nconv_view_warp's src, the loss's tgt) checked and
+// turned into the kernels' PlaneView of one plane plus the channel stride: the strides by flat_view, one
+// plane's extent by view_args. NULL, or "<name>: <why>" kept in text.
+static const char* warp_image_view(const char* name, const float* base, int B, int C, int H, int W, long long bs,
+                                   long long cs, long long rs, nconv::PlaneView& v, long long& vcs,
+                                   std::string& text) {
+    if (const char* why = flat_view(name, B, H, W, B > 1 ? bs : 0, C > 1 ? cs : 0, rs, C, false, text)) return why;
+    if (const char* why = view_args(base, 1, H, W, 4, 0, rs, kNoStrideLimit, 16, kViewPoints, v)) {
+        text = std::string(name) + ": " + why;
+        return text.c_str();
+    }
+    v.bs = B > 1 ? bs : 0;
+    vcs = C > 1 ? cs : 0;
+    return nullptr;
+}
+
+// The descriptor of nconv_view_warp_* / nconv_photo_loss_* checked and turned into the kernels' arguments.
+static const char* warp_args(const nconv_view_warp* d, nconv::WarpArgs& a, std::string& text) {
+    if (!d) return "null descriptor";
+    if (!d->depth || !d->src || !d->k || !d->m) return "null depth, src, k or m";
+    if (d->C != 1 && d->C != 3) return "C must be 1 or 3";
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Hs <= 0 || d->Ws <= 0) return "non-positive B/H/W/Hs/Ws";
+    const int B = d->B, C = d->C, H = d->H, W = d->W, Hs = d->Hs, Ws = d->Ws;
+    if (H > (1 << 24) || W > (1 << 24) || Hs > (1 << 24) || Ws > (1 << 24))
+        return "H, W, Hs and Ws must be at most 2^24 (pixel coordinates are exact floats)";
+    if ((long long)B * C * H * W >= (1LL << 31)) return "batch too large: B * C * H * W must be below 2^31";
+    if (d->k_image_stride < 0 || d->m_image_stride < 0) return "negative k or m image stride";
+    if (!(d->z_min >= 0.f)) return "z_min must be >= 0 (and not NaN)";
+    const float z_max = d->z_max == 0.f ? __FLT_MAX__ : d->z_max;
+    if (!(z_max >= d->z_min)) return "z_max < z_min (or NaN)";
+    if ((size_t)d->depth % 4 || (size_t)d->src % 4 || (size_t)d->k % 4 || (size_t)d->m % 4)
+        return "depth / src / k / m not 4-byte aligned";
+    a = nconv::WarpArgs{};
+    a.B = B, a.C = C, a.H = H, a.W = W, a.Hs = Hs, a.Ws = Ws;
+    if (const char* why = view_args(d->depth, B, H, W, 4, d->depth_image_stride, d->depth_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.depth)) {
+        text = std::string("depth: ") + why;
+        return text.c_str();
+    }
+    if (d->mask) {
+        if (const char* why = view_args(d->mask, B, H, W, 1, d->mask_image_stride, d->mask_row_stride, kNoStrideLimit,
+                                        4, kViewPoints, a.mask)) {
+            text = std::string("mask: ") + why;
+            return text.c_str();
+        }
+    }
+    if (const char* why = warp_image_view("src", d->src, B, C, Hs, Ws, d->src_image_stride, d->src_channel_stride,
+                                          d->src_row_stride, a.src, a.scs, text))
+        return why;
+    a.k = d->k, a.kbs = d->k_image_stride, a.m = d->m, a.mbs = d->m_image_stride;
+    a.z_min = d->z_min, a.z_max = z_max;
+    return nullptr;
+}
+
+int nconv_view_warp_fwd(const struct nconv_view_warp* d, float* warped, unsigned char* valid, void* stream) {
+    const char* fn = "nconv_view_warp_fwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = warp_args(d, a, text)) return fail(-22, fn, why);
+    if (!warped && !valid) return fail(-22, fn, "null warped and valid: nothing to write");
+    if ((size_t)warped % 4) return fail(-22, fn, "warped not 4-byte aligned");
+    return launched(fn, nconv::launch_view_warp_fwd, a, warped, valid, (hipStream_t)stream);
+}
+
+int nconv_view_warp_bwd(const struct nconv_view_warp* d, const float* g_warped, float* g_depth, void* stream) {
+    const char* fn = "nconv_view_warp_bwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = warp_args(d, a, text)) return fail(-22, fn, why);
+    if (!g_warped || !g_depth) return fail(-22, fn, "null g_warped or g_depth");
+    if ((size_t)g_warped % 4 || (size_t)g_depth % 4) return fail(-22, fn, "g_warped / g_depth not 4-byte aligned");
+    return launched(fn, nconv::launch_view_warp_bwd, a, g_warped, g_depth, (hipStream_t)stream);
+}
+
+size_t nconv_photo_loss_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::photo_loss_workspace_bytes(B, H, W);
+}
+
+// The loss's own operands, after warp_args: the target frame and the workspace.
+static const char* photo_args(const nconv_view_warp* d, const float* tgt, long long tbs, long long tcs, long long trs,
+                              const void* ws, size_t ws_bytes, nconv::WarpArgs& a, std::string& text) {
+    if (const char* why = warp_args(d, a, text)) return why;
+    if (!tgt) return "null tgt";
+    if ((size_t)tgt % 4) return "tgt not 4-byte aligned";
+    if (const char* why = warp_image_view("tgt", tgt, a.B, a.C, a.H, a.W, tbs, tcs, trs, a.tgt, a.tcs, text)) return why;
+    if (!ws || ws_bytes < nconv::photo_loss_workspace_bytes(a.B, a.H, a.W)) return "workspace too small";
+    if ((size_t)ws % 8) return "workspace not 8-byte aligned";
+    return nullptr;
+}
+
+int nconv_photo_loss_fwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                         long long tgt_channel_stride, long long tgt_row_stride, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_photo_loss_fwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = photo_args(d, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, workspace,
+                                     workspace_bytes, a, text))
+        return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    if ((size_t)loss % 4) return fail(-22, fn, "loss not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_loss_fwd, a, loss, workspace, (hipStream_t)stream);
+}
+
+int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                         long long tgt_channel_stride, long long tgt_row_stride, const float* gloss,
+                         const void* workspace, size_t workspace_bytes, float* g_depth, void* stream) {
+    const char* fn = "nconv_photo_loss_bwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = photo_args(d, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, workspace,
+                                     workspace_bytes, a, text))
+        return fail(-22, fn, why);
+    if (!g_depth) return fail(-22, fn, "null g_depth");
+    if ((size_t)gloss % 4 || (size_t)g_depth % 4) return fail(-22, fn, "gloss / g_depth not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_loss_bwd, a, gloss, workspace, g_depth, (hipStream_t)stream);
 }
 
 }  // extern "C"

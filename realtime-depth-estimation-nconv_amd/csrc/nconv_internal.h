@@ -467,4 +467,26 @@ struct NearestArgs {
 };
 int launch_depth_nearest(const NearestArgs& a, hipStream_t st, const char** why);
 
+// Depth-driven view warp and photometric loss (nconv_view_warp_*, nconv_photo_loss_*), view_warp.hip.
+struct WarpArgs {
+    int B, C, H, W, Hs, Ws;   // target planes (H, W), source planes (Hs, Ws), C = 1 or 3
+    PlaneView depth;          // fp32 (B, H, W), strides in elements (wide is not used: one pixel per lane)
+    PlaneView mask;           // base null: none; uint8 (B, H, W), strides in bytes; bs 0: one mask for the batch
+    PlaneView src;            // fp32 (B, C, Hs, Ws); rs / bs of one channel plane, channels scs apart
+    long long scs;
+    PlaneView tgt;            // base null: the plain warp; fp32 (B, C, H, W), channels tcs apart
+    long long tcs;
+    const float* k;
+    long long kbs;            // image stride of K in floats (0: one camera)
+    const float* m;
+    long long mbs;            // image stride of m in floats (0: one matrix)
+    float z_min, z_max;
+};
+size_t photo_loss_workspace_bytes(int B, int H, int W);
+int launch_view_warp_fwd(const WarpArgs& a, float* warped, unsigned char* valid, hipStream_t st, const char** why);
+int launch_view_warp_bwd(const WarpArgs& a, const float* g_warped, float* g_depth, hipStream_t st, const char** why);
+int launch_photo_loss_fwd(const WarpArgs& a, float* loss, void* ws, hipStream_t st, const char** why);
+int launch_photo_loss_bwd(const WarpArgs& a, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
+                          const char** why);
+
 }  // namespace nconv
