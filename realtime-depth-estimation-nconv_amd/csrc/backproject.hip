@@ -115,8 +115,7 @@ __global__ __launch_bounds__(kBT) void backproject_count(BackprojectArgs a, int*
 // segment, offsets[B] = the total. One workgroup: kScanT * kScanE segments per round.
 __global__ __launch_bounds__(kScanT) void backproject_scan(int* __restrict__ counts, int nseg, int per_image, int B,
                                                            int* __restrict__ offsets) {
-    __shared__ int wave_sum[kScanT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[kScanT / 64];
     int carry = 0;
     for (int base = 0; base < nseg; base += kScanT * kScanE) {
         const int idx = base + (int)threadIdx.x * kScanE;
@@ -126,22 +125,8 @@ __global__ __launch_bounds__(kScanT) void backproject_scan(int* __restrict__ cou
             v[k] = idx + k < nseg ? counts[idx + k] : 0;
             mine += v[k];
         }
-        int inc = mine;  // inclusive scan over the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wave_sum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < kScanT / 64; ++q) {
-            const int t = wave_sum[q];
-            before += q < wave ? t : 0;
-            total += t;
-        }
-        int ex = carry + before + inc - mine;
+        int total;
+        int ex = carry + block_excl_scan<kScanT / 64>(mine, s_wave, total);
 #pragma unroll
         for (int k = 0; k < kScanE; ++k) {
             if (idx + k < nseg) {
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(kScanT) void backproject_scan(int* __restrict__ cou
             ex += v[k];
         }
         carry += total;
-        __syncthreads();  // wave_sum is rewritten in the next round
+        __syncthreads();  // s_wave is rewritten in the next round
     }
     if (threadIdx.x == 0) offsets[B] = carry;
 }

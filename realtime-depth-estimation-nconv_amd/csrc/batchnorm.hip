@@ -31,16 +31,7 @@ namespace nconv {
 constexpr int kBT = 256;
 constexpr int kChunk = 4096;
 constexpr int kPer = kChunk / kBT;  // elements per thread
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();  // red is reused between calls
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+// The block sums are wave_ops.h's block_sum4_again: a kernel passes the same red to each of its calls.
 
 // Loads the thread's kPer elements of chunk j of plane (b, c): element i = j*kChunk + 4*tid + k
 // (+ kBT*4 per float4 group); out-of-plane elements are flagged invalid.
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(kBT) void bn_stats(const float* __restrict__ x, int
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) s += v[k];  // invalid elements are 0
-    const float mean = block_sum(s, red) / (float)n;
+    const float mean = block_sum4_again(s, red) / (float)n;
     float m2 = 0.f, sd = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
@@ -106,8 +97,8 @@ __global__ __launch_bounds__(kBT) void bn_stats(const float* __restrict__ x, int
         m2 = fmaf(d, d, m2);
         sd += d;
     }
-    m2 = block_sum(m2, red);
-    sd = block_sum(sd, red);
+    m2 = block_sum4_again(m2, red);
+    sd = block_sum4_again(sd, red);
     if (threadIdx.x == 0) {
         float* o = part + ((size_t)c * nparts + (size_t)b * ncp + j) * 4;
         o[0] = (float)n;
@@ -245,9 +236,9 @@ __global__ __launch_bounds__(kBT) void bn_bwd_stats(const float* __restrict__ gy
         sx = fmaf(gg, d, sx);
         sd += ok[k] ? d : 0.f;
     }
-    s = block_sum(s, red);
-    sx = block_sum(sx, red);
-    sd = block_sum(sd, red);
+    s = block_sum4_again(s, red);
+    sx = block_sum4_again(sx, red);
+    sd = block_sum4_again(sd, red);
     if (threadIdx.x == 0) {
         float* o = part + ((size_t)c * nparts + (size_t)b * ncp + j) * 3;
         o[0] = s;
@@ -334,7 +325,7 @@ __global__ __launch_bounds__(kBT) void relu_bias_stats(const float* __restrict__
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) s += v[k];
-    s = block_sum(s, red);
+    s = block_sum4_again(s, red);
     if (threadIdx.x == 0) part[(size_t)c * nparts + (size_t)b * ncp + j] = s;
 }
 

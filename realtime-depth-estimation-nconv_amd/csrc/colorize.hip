@@ -41,8 +41,6 @@ constexpr int kAW = kTW + 2 * kMaxR;  // row pitch of the staged tile with its h
 constexpr int kAH = kTH + 2 * kMaxR;
 constexpr int kRangeChunks = 32;    // workgroups per image of the range pass
 
-int tiles_per_image(int H, int W) { return ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW); }
-
 // fp32 -> uint32 whose unsigned order is the float order (-0 below +0), and back
 __device__ __forceinline__ unsigned range_key(float v) {
     const unsigned u = __float_as_uint(v);
@@ -75,14 +73,6 @@ __device__ __forceinline__ unsigned pix24(const unsigned (&d)[3], int k) {
     }
 }
 
-// the tile of this workgroup: image b, first row of this wave i0, first pixel of this lane j
-__device__ __forceinline__ void tile_of(const ColorizeArgs& a, int& b, int& ti, int& tj) {
-    const int ntw = (a.W + kTW - 1) / kTW, per = ntw * ((a.H + kTH - 1) / kTH);
-    b = blockIdx.x / per;
-    const int t = blockIdx.x - b * per;
-    ti = (t / ntw) * kTH, tj = (t % ntw) * kTW;
-}
-
 __global__ __launch_bounds__(kT) void colorize_range_reset(unsigned* __restrict__ range, unsigned n) {
     const unsigned t = blockIdx.x * (unsigned)kT + threadIdx.x;  // n = 2 B < 2^32
     if (t < n) range[t] = (t & 1) ? 0u : 0xffffffffu;
@@ -92,12 +82,14 @@ __global__ __launch_bounds__(kT) void colorize_range_reset(unsigned* __restrict_
 // so at most kRangeChunks pairs meet on an image's two keys
 __global__ __launch_bounds__(kT) void colorize_range(ColorizeArgs a, int chunks) {
     __shared__ unsigned s_min[kT / 64], s_max[kT / 64];
-    const int ntw = (a.W + kTW - 1) / kTW, per = ntw * ((a.H + kTH - 1) / kTH);
+    const int per = tiles_per_image<kTH, kTW>(a.H, a.W);
     const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
     const __amdgpu_buffer_rsrc_t r = plane_rsrc(a.d.image<float>(b), view_bytes(a.H, a.d.rs, a.W, 4));
     unsigned kmin = 0xffffffffu, kmax = 0u;
     for (int t = chunk; t < per; t += chunks) {
-        const int i0 = (t / ntw) * kTH + (threadIdx.x >> 6) * kR, j = (t % ntw) * kTW + (threadIdx.x & 63) * 4;
+        int i0, j;
+        tile_corner<kTH, kTW>(a.W, t, i0, j);
+        i0 += (threadIdx.x >> 6) * kR, j += (threadIdx.x & 63) * 4;
         const int n = min(4, a.W - j);  // <= 0: the lane is past the row
         f4 v[kR];
 #pragma unroll
@@ -140,8 +132,8 @@ __global__ __launch_bounds__(kT) void colorize_map(ColorizeArgs a) {
     __shared__ __attribute__((aligned(16))) float s_a[SPLAT ? kAH * kAW : 4];  // the tile and its halo
     __shared__ __attribute__((aligned(16))) float s_b[SPLAT ? kAH * kTW : 4];  // its row minima
     const float kNone = __builtin_inff();  // an empty pixel among the window's candidates
-    int b, ti, tj;
-    tile_of(a, b, ti, tj);
+    const TileOrigin o = tile_origin<kTH, kTW>(a.H, a.W);
+    const int b = o.b, ti = o.i0, tj = o.j0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i0 = ti + wave * kR, j = tj + lane * 4;
     {
@@ -239,11 +231,11 @@ __global__ __launch_bounds__(kT) void colorize_map(ColorizeArgs a) {
 }  // namespace
 
 int launch_depth_colorize(const ColorizeArgs& a, hipStream_t st, const char** why) {
-    const dim3 grid((unsigned)a.B * (unsigned)tiles_per_image(a.H, a.W));
+    const dim3 grid((unsigned)a.B * (unsigned)tiles_per_image<kTH, kTW>(a.H, a.W));
     if (a.auto_range) {
         const unsigned keys = 2u * (unsigned)a.B;
         hipLaunchKernelGGL(colorize_range_reset, dim3((keys - 1) / kT + 1), dim3(kT), 0, st, a.range, keys);
-        const int chunks = std::min(tiles_per_image(a.H, a.W), kRangeChunks);
+        const int chunks = std::min(tiles_per_image<kTH, kTW>(a.H, a.W), kRangeChunks);
         hipLaunchKernelGGL(colorize_range, dim3((unsigned)a.B * (unsigned)chunks), dim3(kT), 0, st, a, chunks);
     }
     if (a.radius > 0)

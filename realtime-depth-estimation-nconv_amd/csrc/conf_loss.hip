@@ -12,11 +12,11 @@
 //
 // Every operation in fp32 in the order written (include/nconv.h), no contraction. lam is a device
 // scalar, so a captured training step decays it per epoch without another capture. On the loss's
-// 16 x 64 pixel tiles, four consecutive pixels of a row per thread (plane_io.h's load4_f32):
+// 16 x 64 pixel tiles, four consecutive pixels of a row per thread (plane_io.h's loss_quad):
 //   conf_loss_partials  one workgroup per tile of one image: the tile's 1024 terms summed in fp32
-//                       (a thread's four in order, the xor tree over the lanes, the four waves in order)
-//   conf_loss_finalize  one block: a wave per image sums its tiles in a fixed order in double, then
-//                       thread 0 adds the images in order and writes L
+//                       (a thread's four in order, then wave_ops.h's block_sum4)
+//   conf_loss_finalize  one block: a wave per image sums its tiles (image_tile_sums), then thread 0
+//                       adds the images in order and writes L
 //   conf_loss_grad      one workgroup per tile: g_r, g_c (contiguous B x H x W), overwritten
 // Deterministic (no atomics), no host synchronisation.
 #include "nconv_internal.h"
@@ -25,9 +25,6 @@ namespace nconv {
 
 constexpr int kCT = 256;
 constexpr int kCF = 1024;            // finalize: sixteen waves, one image each at a time
-constexpr int kCH = 16, kCW = 64;    // pixel tile of one workgroup (4 consecutive pixels per thread)
-
-static int conf_tiles_per_image(int H, int W) { return ((H + kCH - 1) / kCH) * ((W + kCW - 1) / kCW); }
 
 // e and de of one pixel (KIND: enum nconv_conf_loss_err)
 template <int KIND>
@@ -52,58 +49,32 @@ __device__ __forceinline__ float conf_term(float r, float c, float t, float beta
     return t != 0.f ? e - (lam * c) * (1.0f - e) : 0.f;
 }
 
-struct ConfTile {
-    int b, i, j, n;  // image; the thread's row and first column; how many of its four pixels are in the row
-    bool row_in;
-};
-__device__ __forceinline__ ConfTile conf_tile(const ConfLossArgs& a) {
-    const int ntw = (a.W + kCW - 1) / kCW, nth = (a.H + kCH - 1) / kCH;
-    ConfTile q;
-    q.b = blockIdx.x / (ntw * nth);
-    const int t = blockIdx.x - q.b * ntw * nth;
-    q.i = (t / ntw) * kCH + (threadIdx.x >> 4);
-    q.j = (t % ntw) * kCW + (threadIdx.x & 15) * 4;
-    q.row_in = q.i < a.H;
-    q.n = min(4, a.W - q.j);
-    return q;
-}
-// the thread's four pixels of one view; pixels outside the plane read 0 (t = 0: no term, no gradient)
-__device__ __forceinline__ f4 conf_load(const PlaneView& p, const ConfLossArgs& a, const ConfTile& q) {
-    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(p.image<float>(q.b), view_bytes(a.H, p.rs, a.W, 4));
-    return load4_f32(rs, p.wide != 0, q.row_in, q.n, (unsigned)((long long)q.i * p.rs + q.j) * 4u);
-}
-
 // one workgroup per tile; part[tile], tiles of image b at b * tiles-per-image (a fixed order)
 template <int KIND>
 __global__ __launch_bounds__(kCT) void conf_loss_partials(ConfLossArgs a, float* __restrict__ part) {
 #pragma clang fp contract(off)
     __shared__ float red[kCT / 64];
-    const ConfTile q = conf_tile(a);
-    const f4 rv = conf_load(a.r, a, q), cv = conf_load(a.c, a, q), tv = conf_load(a.t, a, q);
+    const Quad q = loss_quad(a.H, a.W);
+    // pixels outside the plane read 0 (t = 0: no term, no gradient)
+    const f4 rv = load4_f32(a.r, a.H, a.W, q), cv = load4_f32(a.c, a.H, a.W, q), tv = load4_f32(a.t, a.H, a.W, q);
     const float lam = a.lam[0], beta = a.beta;
     float s = conf_term<KIND>(rv.x, cv.x, tv.x, beta, lam);
     s += conf_term<KIND>(rv.y, cv.y, tv.y, beta, lam);
     s += conf_term<KIND>(rv.z, cv.z, tv.z, beta, lam);
     s += conf_term<KIND>(rv.w, cv.w, tv.w, beta, lam);
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    s = block_sum4(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// One block. Wave w reduces images w, w + 16, ..: lane l adds tiles l, l + 64, .. in order (double),
-// then the xor tree over the lanes -> img[b]. After the barrier thread 0 adds img[0..B) in order.
+// One block. Wave w reduces images w, w + 16, .. (image_tile_sums) -> img[b]. After the barrier
+// thread 0 adds img[0..B) in order.
 __global__ __launch_bounds__(kCF) void conf_loss_finalize(const float* __restrict__ part, int B, int tiles, double n,
                                                            double* __restrict__ img, float* __restrict__ loss) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int b = w; b < B; b += kCF / 64) {
-        const float* pb = part + (size_t)b * tiles;
-        double s = 0.0;
-        for (int t = lane; t < tiles; t += 64) s += (double)pb[t];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
-        if (lane == 0) img[b] = s;
+        double s[1];
+        image_tile_sums(part + (size_t)b * tiles, tiles, lane, s);
+        if (lane == 0) img[b] = s[0];
     }
     __syncthreads();  // img written by this block's waves
     if (threadIdx.x == 0) {
@@ -117,8 +88,9 @@ template <int KIND>
 __global__ __launch_bounds__(kCT) void conf_loss_grad(ConfLossArgs a, const float* __restrict__ gloss,
                                                        float* __restrict__ g_r, float* __restrict__ g_c) {
 #pragma clang fp contract(off)
-    const ConfTile q = conf_tile(a);
-    const f4 rv = conf_load(a.r, a, q), cv = conf_load(a.c, a, q), tv = conf_load(a.t, a, q);
+    const Quad q = loss_quad(a.H, a.W);
+    // pixels outside the plane read 0 (t = 0: no term, no gradient)
+    const f4 rv = load4_f32(a.r, a.H, a.W, q), cv = load4_f32(a.c, a.H, a.W, q), tv = load4_f32(a.t, a.H, a.W, q);
     const float lam = a.lam[0], beta = a.beta;
     const float n = (float)((long long)a.B * a.H * a.W);
     const float k = (gloss ? gloss[0] : 1.f) * (1.0f / n);
@@ -137,11 +109,11 @@ __global__ __launch_bounds__(kCT) void conf_loss_grad(ConfLossArgs a, const floa
 }
 
 size_t conf_loss_workspace_bytes(int B, int H, int W) {
-    return (size_t)B * sizeof(double) + (size_t)B * conf_tiles_per_image(H, W) * sizeof(float);
+    return (size_t)B * sizeof(double) + (size_t)B * loss_tiles_per_image(H, W) * sizeof(float);
 }
 
 int launch_conf_loss_fwd(const ConfLossArgs& a, float* loss, void* ws, hipStream_t st, const char** why) {
-    const int tiles = conf_tiles_per_image(a.H, a.W);
+    const int tiles = loss_tiles_per_image(a.H, a.W);
     double* img = (double*)ws;
     float* part = (float*)(img + a.B);
     const dim3 g(a.B * tiles), t(kCT);
@@ -156,7 +128,7 @@ int launch_conf_loss_fwd(const ConfLossArgs& a, float* loss, void* ws, hipStream
 
 int launch_conf_loss_bwd(const ConfLossArgs& a, const float* gloss, float* g_r, float* g_c, hipStream_t st,
                          const char** why) {
-    const dim3 g(a.B * conf_tiles_per_image(a.H, a.W)), t(kCT);
+    const dim3 g(a.B * loss_tiles_per_image(a.H, a.W)), t(kCT);
     if (a.kind == NCONV_CONF_LOSS_SMOOTH_L1)
         hipLaunchKernelGGL(conf_loss_grad<NCONV_CONF_LOSS_SMOOTH_L1>, g, t, 0, st, a, gloss, g_r, g_c);
     else

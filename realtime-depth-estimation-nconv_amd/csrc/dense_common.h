@@ -29,12 +29,4 @@ __device__ __forceinline__ void dsplit3(const float (&v)[8], dbf16x8 (&o)[3]) {
     }
 }
 
-// the status of the launches a dense launcher just issued: 0, or -5 with *why set
-static inline int dense_launched(const char** why) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    *why = hipGetErrorString(e);
-    return -5;
-}
-
 }  // namespace nconv

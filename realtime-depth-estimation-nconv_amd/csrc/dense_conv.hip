@@ -657,20 +657,20 @@ int launch_dense_conv(const nconv_dense_conv& p, hipStream_t st, const char** wh
             nt == 9 ? go_dense_bf9_k<32, 9>(p, sc, st) : go_dense_bf9_k<32, 6>(p, sc, st);
         else
             nt == 9 ? go_dense_bf9_k<64, 9>(p, sc, st) : go_dense_bf9_k<64, 6>(p, sc, st);
-        return dense_launched(why);
+        return launch_status(why);
     }
     if (!(co == 32 ? go_dense_k<32>(p, sc, st) : go_dense_k<64>(p, sc, st))) {
         *why = "no dense-conv kernel for this (kind, stride, shortcut) combination";
         return -95;
     }
-    return dense_launched(why);
+    return launch_status(why);
 }
 
 int launch_conv3x3_c1(const float* x, int B, int Cin, int H, int W, const float* w, const float* res, float* out,
                       hipStream_t st, const char** why) {
     const int ntx = (W + 63) / 64, nty = (H + 15) / 16;
     hipLaunchKernelGGL(conv3x3_c1, dim3(ntx * nty * B), dim3(kDT), 0, st, x, Cin, H, W, w, res, out, ntx, nty);
-    return dense_launched(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

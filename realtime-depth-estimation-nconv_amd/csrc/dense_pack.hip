@@ -163,7 +163,7 @@ int launch_dense_pack(int kind, int Cin, int Cout, const float* w, const float* 
             hipLaunchKernelGGL(dense_pack3x3<32>, dim3(nb), dim3(64), 0, st, Cin, Cout, w, scale, wp);
         else
             hipLaunchKernelGGL(dense_pack3x3<64>, dim3(nb), dim3(64), 0, st, Cin, Cout, w, scale, wp);
-        return dense_launched(why);
+        return launch_status(why);
     }
     const size_t n = dense_fp32_floats(kind, Cin, Cout);
     size_t blocks = (n + kDT - 1) / kDT;
@@ -177,7 +177,7 @@ int launch_dense_pack(int kind, int Cin, int Cout, const float* w, const float* 
         hipLaunchKernelGGL(dense_pack_bf9, dim3(b9), dim3(kDT), 0, st, kind, Cin, Cout, dense_cout_tile(Cout), w,
                            scale, reinterpret_cast<unsigned char*>(wp + n), rows);
     }
-    return dense_launched(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

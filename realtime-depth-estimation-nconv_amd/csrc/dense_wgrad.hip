@@ -378,16 +378,14 @@ __global__ __launch_bounds__(256) void dense_wgrad_tr_rows(const float* __restri
             acc[j][kha + 2][1] = __builtin_fma(g, (double)x11, acc[j][kha + 2][1]);
         }
     }
-    // the workgroup's 16 (x C1) tap sums: wave butterflies, then the four waves in order
+    // the workgroup's 16 (x C1) tap sums in wave_ops.h's order
 #pragma unroll
     for (int j = 0; j < kTrMaxC1; ++j) {
         if (j >= C1) continue;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const int kh = t >> 2, kw = t & 3;
-            double v = (kw & 1) == kwa ? acc[j][kh][kw >> 1] : 0.0;
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+            const double v = wave_sum((kw & 1) == kwa ? acc[j][kh][kw >> 1] : 0.0);
             if (lane == 0) red[wv][j * 16 + t] = v;
         }
     }
@@ -395,7 +393,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_tr_rows(const float* __restri
     if (tid < C1 * 16) {
         const int j = tid >> 4, t = tid & 15;
         const size_t slice = ((size_t)b * nry + ry) * nrx + rx;
-        part[(slice * C1 + j) * (size_t)(Cout * 16) + co * 16 + t] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        part[(slice * C1 + j) * (size_t)(Cout * 16) + co * 16 + t] = waves_in_order(&red[0][tid], kTrMaxC1 * 16);
     }
 }
 
@@ -754,7 +752,7 @@ static int launch_dense_wgrad_main(const nconv_dense_wgrad& g, float* ws, hipStr
     }
     const int mn = pl.a.M * pl.a.N;
     hipLaunchKernelGGL(dense_wgrad_reduce<float>, dim3((mn + 63) / 64), dim3(kDT), 0, st, ws, pl.a.nks, mn, g.gw);
-    return dense_launched(why);
+    return launch_status(why);
 }
 
 int launch_dense_wgrad(const nconv_dense_wgrad& g, float* ws, size_t ws_bytes, hipStream_t st, const char** why) {
@@ -775,7 +773,7 @@ int launch_dense_wgrad(const nconv_dense_wgrad& g, float* ws, size_t ws_bytes, h
     const int mn = cs * g.Cout * 16;
     hipLaunchKernelGGL(dense_wgrad_reduce<double>, dim3((mn + 63) / 64), dim3(kDT), 0, st, part, r.nslice, mn,
                        sp == 1 ? g.gw + (size_t)g.C0 * g.Cout * 16 : g.gw);
-    return dense_launched(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

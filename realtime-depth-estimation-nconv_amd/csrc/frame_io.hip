@@ -28,8 +28,6 @@ constexpr int kIR = 2;               // rows per wave
 constexpr int kIH = kIT / 64 * kIR;  // rows per tile
 constexpr int kIW = 64 * 4;          // pixels per tile row (four per lane)
 
-static int frame_tiles_per_image(int H, int W) { return ((H + kIH - 1) / kIH) * ((W + kIW - 1) / kIW); }
-
 __device__ __forceinline__ unsigned ld_u16(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
 }
@@ -118,9 +116,8 @@ __device__ __forceinline__ void ingest_plane(const IngestArgs& a, const IngestPl
 
 // grid (B * tiles per image, jobs); job0..2: 0 = RGB, 1 / 2 = plane 0 / 1 (the host lists the present ones)
 __global__ __launch_bounds__(kIT) void frame_ingest(IngestArgs a, int job0, int job1, int job2) {
-    const int ntw = (a.w + kIW - 1) / kIW, per = ntw * ((a.h + kIH - 1) / kIH);
-    const int b = blockIdx.x / per, t = blockIdx.x - b * per;
-    const int i0 = (t / ntw) * kIH + (threadIdx.x >> 6) * kIR, j = (t % ntw) * kIW + (threadIdx.x & 63) * 4;
+    const TileOrigin o = tile_origin<kIH, kIW>(a.h, a.w);
+    const int b = o.b, i0 = o.i0 + (threadIdx.x >> 6) * kIR, j = o.j0 + (threadIdx.x & 63) * 4;
     const int job = blockIdx.y == 0 ? job0 : blockIdx.y == 1 ? job1 : job2;
     if (job == 0) {
         ingest_rgb(a, b, i0, j);
@@ -152,9 +149,8 @@ __device__ __forceinline__ void export_pair(unsigned short* p, unsigned lo, unsi
 }
 
 __global__ __launch_bounds__(kIT) void depth_export(ExportArgs a) {
-    const int ntw = (a.W + kIW - 1) / kIW, per = ntw * ((a.H + kIH - 1) / kIH);
-    const int b = blockIdx.x / per, t = blockIdx.x - b * per;
-    const int i0 = (t / ntw) * kIH + (threadIdx.x >> 6) * kIR, j = (t % ntw) * kIW + (threadIdx.x & 63) * 4;
+    const TileOrigin o = tile_origin<kIH, kIW>(a.H, a.W);
+    const int b = o.b, i0 = o.i0 + (threadIdx.x >> 6) * kIR, j = o.j0 + (threadIdx.x & 63) * 4;
     const __amdgpu_buffer_rsrc_t r = plane_rsrc(a.d.image<float>(b), view_bytes(a.H, a.d.rs, a.W, 4));
     const int n = min(4, a.W - j);
     f4 v[kIR];
@@ -188,13 +184,13 @@ int launch_frame_ingest(const IngestArgs& a, hipStream_t st, const char** why) {
     if (a.rgb.base) jobs[nj++] = 0;
     if (a.pl[0].src.base) jobs[nj++] = 1;
     if (a.pl[1].src.base) jobs[nj++] = 2;
-    hipLaunchKernelGGL(frame_ingest, dim3(a.B * frame_tiles_per_image(a.h, a.w), nj), dim3(kIT), 0, st, a, jobs[0],
+    hipLaunchKernelGGL(frame_ingest, dim3(a.B * tiles_per_image<kIH, kIW>(a.h, a.w), nj), dim3(kIT), 0, st, a, jobs[0],
                        jobs[1], jobs[2]);
     return launch_status(why);
 }
 
 int launch_depth_export(const ExportArgs& a, hipStream_t st, const char** why) {
-    hipLaunchKernelGGL(depth_export, dim3(a.B * frame_tiles_per_image(a.H, a.W)), dim3(kIT), 0, st, a);
+    hipLaunchKernelGGL(depth_export, dim3(a.B * tiles_per_image<kIH, kIW>(a.H, a.W)), dim3(kIT), 0, st, a);
     return launch_status(why);
 }
 

@@ -141,9 +141,8 @@ __global__ __launch_bounds__(kT) void ipbasic_tile(IpbasicArgs a) {
     __shared__ unsigned sA[ROWS * P], sB[ROWS * P];
     const int tid = (int)threadIdx.x;
     const int H = a.H, W = a.W;
-    const int ntw = (W + kTW - 1) / kTW, per = ntw * ((H + kTH - 1) / kTH);
-    const int b = blockIdx.x / per, t = blockIdx.x - b * per;
-    const int oy = (t / ntw) * kTH - HALO, ox = (t % ntw) * kTW - HALO;  // the image coordinates of local (0, 0)
+    const TileOrigin o = tile_origin<kTH, kTW>(H, W);
+    const int b = o.b, oy = o.i0 - HALO, ox = o.j0 - HALO;  // the image coordinates of local (0, 0)
     const __amdgpu_buffer_rsrc_t r = plane_rsrc(a.s.image<float>(b), view_bytes(H, a.s.rs, W, 4));
     auto inside = [&](int ly, int lx) {
         return (unsigned)(oy + ly) < (unsigned)H && (unsigned)(ox + lx) < (unsigned)W;
@@ -301,7 +300,7 @@ __global__ __launch_bounds__(kT) void ipbasic_tile(IpbasicArgs a) {
 int launch_depth_ipbasic(const IpbasicArgs& a, hipStream_t st, const char** why) {
     static_assert(2 * Geo<kAll>::ROWS * Geo<kAll>::P * 4 <= 160 * 1024 / 2, "two workgroups per CU without extrapolate");
     static_assert(2 * Geo<kBack>::ROWS * Geo<kBack>::P * 4 <= 160 * 1024, "the extrapolation's tile fits the LDS");
-    const long long tiles = (long long)((a.H + kTH - 1) / kTH) * ((a.W + kTW - 1) / kTW);
+    const long long tiles = tiles_per_image<kTH, kTW>(a.H, a.W);
     const dim3 grid((unsigned)(a.B * tiles));  // <= B * H * W < 2^31
     if (!a.extrapolate) {
         hipLaunchKernelGGL(ipbasic_tile<kAll>, grid, dim3(kT), 0, st, a);

@@ -9,10 +9,11 @@
 // On B planes of (H, W): the training loop calls it on the whole (B, 1, H, W) batch
 // (train_step1.py:63; the means run over B*H*W, the Sobel convolutions pad each image on its own),
 // the validation loop on element [0] (utils.py:36, B = 1). In PyTorch this is ~45 elementwise /
-// reduction launches forward and backward; here, on 16 x 64 pixel tiles whose diff window
+// reduction launches forward and backward; here, on the 16 x 64 pixel tiles of plane_io.h whose diff window
 // (diff = t - masked r, 2-pixel halo, zero outside the image) is staged once in LDS:
 //   loss_partials  per tile: e^2, |gx|, |gy| (the same operation order as train.gradient_x / _y,
-//                  so signs match torch exactly), one per-tile partial of each
+//                  so signs match torch exactly), one per-tile partial of each (wave_ops.h's
+//                  block_sum4_again of the threads' sums)
 //   loss_finalize  one block: fixed-order (double) sum of the tile partials -> L and the two
 //                  backward coefficients, kept in the workspace for the backward
 //   loss_grad      per tile: the signs of gx, gy over the tile + 1-pixel halo into LDS, then
@@ -25,9 +26,8 @@
 namespace nconv {
 
 constexpr int kLT = 256;
-constexpr int kTH = 16, kTW = 64;                // pixel tile of one workgroup (4 pixels per thread)
-constexpr int kDH = kTH + 4, kDW = kTW + 4;      // staged diff window (2-pixel halo)
-constexpr int kSH = kTH + 2, kSW = kTW + 2;      // sign window (1-pixel halo)
+constexpr int kDH = kLossTH + 4, kDW = kLossTW + 4;  // staged diff window (2-pixel halo)
+constexpr int kSH = kLossTH + 2, kSW = kLossTW + 2;  // sign window (1-pixel halo)
 
 struct LossPlane {
     const float* r;
@@ -68,22 +68,7 @@ __device__ __forceinline__ float sobel_y(D d, int i, int j) {
     return (a + 2.f * b) + c;
 }
 
-// Tiles of the grid: (tiles per image row band) x (row bands) x B, blockIdx.x linear.
-struct LossTile {
-    int b, i0, j0;
-};
-__device__ __forceinline__ LossTile loss_tile(const LossPlane& p) {
-    const int ntw = (p.W + kTW - 1) / kTW, nth = (p.H + kTH - 1) / kTH;
-    const int t = blockIdx.x;
-    LossTile lt;
-    lt.b = t / (ntw * nth);
-    const int r = t - lt.b * ntw * nth;
-    lt.i0 = (r / ntw) * kTH;
-    lt.j0 = (r % ntw) * kTW;
-    return lt;
-}
-
-// The tile's diff window (rows i0-2 .. i0+kTH+1, columns j0-2 .. j0+kTW+1) into LDS: every
+// The tile's diff window (rows i0-2 .. i0+kLossTH+1, columns j0-2 .. j0+kLossTW+1) into LDS: every
 // element's t and r loaded first (buffer loads, out-of-plane offsets read 0; r also where t == 0,
 // so no load waits on another), then diff = t - masked_fill(r, t == 0, 0).
 __device__ __forceinline__ void stage_diff(const LossPlane& p, int i0, int j0, float* dw) {
@@ -106,21 +91,11 @@ __device__ __forceinline__ void stage_diff(const LossPlane& p, int i0, int j0, f
     }
 }
 
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // one workgroup per tile; the partial sums are indexed by tile (a fixed order)
 __global__ __launch_bounds__(kLT) void loss_partials(LossPlane pb, int grad_loss, float* __restrict__ part) {
     __shared__ float dw[kDH * kDW];
     __shared__ float red[4];
-    const LossTile lt = loss_tile(pb);
+    const TileOrigin lt = tile_origin<kLossTH, kLossTW>(pb.H, pb.W);
     const LossPlane p = pb.image(lt.b);
     stage_diff(p, lt.i0, lt.j0, dw);
     __syncthreads();
@@ -128,8 +103,8 @@ __global__ __launch_bounds__(kLT) void loss_partials(LossPlane pb, int grad_loss
     auto d = [&](int a, int b) { return dw[(a - lt.i0 + 2) * kDW + (b - lt.j0 + 2)]; };
     float sq = 0.f, ax = 0.f, ay = 0.f;
 #pragma unroll
-    for (int k = 0; k < kTH * kTW / kLT; ++k) {
-        const int e = threadIdx.x + kLT * k, i = lt.i0 + e / kTW, j = lt.j0 + e % kTW;
+    for (int k = 0; k < kLossTH * kLossTW / kLT; ++k) {
+        const int e = threadIdx.x + kLT * k, i = lt.i0 + e / kLossTW, j = lt.j0 + e % kLossTW;
         if (i < p.H && j < p.W) {
             const float dv = d(i, j);
             sq += dv * dv;  // (rec - t)^2
@@ -139,9 +114,9 @@ __global__ __launch_bounds__(kLT) void loss_partials(LossPlane pb, int grad_loss
             }
         }
     }
-    sq = block_sum256(sq, red);
-    ax = block_sum256(ax, red);
-    ay = block_sum256(ay, red);
+    sq = block_sum4_again(sq, red);
+    ax = block_sum4_again(ax, red);
+    ay = block_sum4_again(ay, red);
     if (threadIdx.x == 0) {
         part[3 * blockIdx.x] = sq;
         part[3 * blockIdx.x + 1] = ax;
@@ -150,6 +125,7 @@ __global__ __launch_bounds__(kLT) void loss_partials(LossPlane pb, int grad_loss
 }
 
 // coef[0] = L, coef[1] = dL/d(e^2 sum) factor c_e (dL/de = c_e e), coef[2] = c_g (0.2 / n)
+// (its own LDS tree over 256 doubles, not image_tile_sums: that order would change the loss's bits)
 __global__ __launch_bounds__(kLT) void loss_finalize(const float* __restrict__ part, int nblk, int n, int grad_loss,
                                                       float* __restrict__ loss, float* __restrict__ coef) {
     __shared__ double red[3][kLT];
@@ -189,7 +165,7 @@ __global__ __launch_bounds__(kLT) void loss_grad(LossPlane pb, int grad_loss, co
                                                   const float* __restrict__ gout, float* __restrict__ g) {
     __shared__ float dw[kDH * kDW];
     __shared__ float sgx[kSH * kSW], sgy[kSH * kSW];
-    const LossTile lt = loss_tile(pb);
+    const TileOrigin lt = tile_origin<kLossTH, kLossTW>(pb.H, pb.W);
     const LossPlane p = pb.image(lt.b);
     const int n = p.H * p.W;
     g += (size_t)lt.b * n;  // contiguous (B, H, W) gradient
@@ -210,8 +186,8 @@ __global__ __launch_bounds__(kLT) void loss_grad(LossPlane pb, int grad_loss, co
     const float go = gout ? gout[0] : 1.f;
     const float ce = coef[1], cg = coef[2];
 #pragma unroll
-    for (int k = 0; k < kTH * kTW / kLT; ++k) {
-        const int e = threadIdx.x + kLT * k, li = e / kTW, lj = e % kTW, i = lt.i0 + li, j = lt.j0 + lj;
+    for (int k = 0; k < kLossTH * kLossTW / kLT; ++k) {
+        const int e = threadIdx.x + kLT * k, li = e / kLossTW, lj = e % kLossTW, i = lt.i0 + li, j = lt.j0 + lj;
         if (i >= p.H || j >= p.W) continue;
         if (p.t[i * p.ts + j] == 0.f) {  // masked_fill: no gradient reaches r here
             g[i * p.W + j] = 0.f;
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(kLT) void loss_grad(LossPlane pb, int grad_loss, co
     }
 }
 
-static int loss_tiles(int B, int H, int W) { return B * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW); }
+static int loss_tiles(int B, int H, int W) { return B * loss_tiles_per_image(H, W); }
 
 size_t loss_workspace_bytes(int B, int H, int W) { return (3 * (size_t)loss_tiles(B, H, W) + 4) * sizeof(float); }
 

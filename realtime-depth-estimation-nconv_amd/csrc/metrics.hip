@@ -8,12 +8,12 @@
 //           7 sum(1/p - 1/g)^2  8 sum(ln p - ln g)^2  9-11 #{max(p/g, g/p) < 1.25, 1.25^2, 1.25^3}
 //
 // In PyTorch these are ~40 elementwise / reduction launches per frame; here, on the loss's 16 x 64
-// pixel tiles (four consecutive pixels of a row per thread, read from the two views with plane_io.h's
-// load4_f32):
+// pixel tiles (four consecutive pixels of a row per thread: plane_io.h's loss_quad):
 //   metrics_partials  one workgroup per tile of one image: the per-pixel terms in fp32 (IEEE division,
-//                     logf, no contraction), twelve fp32 tile partials (counts <= 1024 are exact)
-//   metrics_finalize  one block of sixteen waves: a wave per image sums its tiles in a fixed order in
-//                     double -> sums[b][0..11]; then accum[k] += image 0, 1, .. B-1 in that order
+//                     logf, no contraction), twelve fp32 tile partials (counts <= 1024 are exact) in
+//                     wave_ops.h's order
+//   metrics_finalize  one block of sixteen waves: a wave per image sums its tiles (image_tile_sums)
+//                     -> sums[b][0..11]; then accum[k] += image 0, 1, .. B-1 in that order
 // Deterministic (no atomics), no host synchronisation, 2 x 4 bytes read per pixel.
 #include "nconv_internal.h"
 
@@ -21,10 +21,7 @@ namespace nconv {
 
 constexpr int kMT = 256;
 constexpr int kFT = 1024;  // finalize: sixteen waves, one image each at a time
-constexpr int kMH = 16, kMW = 64;  // pixel tile of one workgroup (4 consecutive pixels per thread)
 constexpr int kNS = NCONV_DEPTH_METRICS_SUMS;
-
-static int metrics_tiles_per_image(int H, int W) { return ((H + kMH - 1) / kMH) * ((W + kMW - 1) / kMW); }
 
 // one pixel's terms added to the thread's twelve sums
 __device__ __forceinline__ void metrics_pixel(float pr, float g, const MetricsArgs& a, float (&s)[kNS]) {
@@ -55,15 +52,8 @@ __device__ __forceinline__ void metrics_pixel(float pr, float g, const MetricsAr
 // one workgroup per tile; part[tile][0..11], tiles of image b at b * tiles-per-image (a fixed order)
 __global__ __launch_bounds__(kMT) void metrics_partials(MetricsArgs a, float* __restrict__ part) {
     __shared__ float red[kMT / 64][kNS];
-    const int ntw = (a.W + kMW - 1) / kMW, nth = (a.H + kMH - 1) / kMH;
-    const int b = blockIdx.x / (ntw * nth), t = blockIdx.x - b * ntw * nth;
-    const int i = (t / ntw) * kMH + (threadIdx.x >> 4), j = (t % ntw) * kMW + (threadIdx.x & 15) * 4;
-    const __amdgpu_buffer_rsrc_t rp = plane_rsrc(a.p.image<float>(b), view_bytes(a.H, a.p.rs, a.W, 4));
-    const __amdgpu_buffer_rsrc_t rg = plane_rsrc(a.g.image<float>(b), view_bytes(a.H, a.g.rs, a.W, 4));
-    const bool row_in = i < a.H;  // pixels outside the plane read 0 (an invalid target)
-    const int n = min(4, a.W - j);
-    const f4 pv = load4_f32(rp, a.p.wide != 0, row_in, n, (unsigned)((long long)i * a.p.rs + j) * 4u);
-    const f4 gv = load4_f32(rg, a.g.wide != 0, row_in, n, (unsigned)((long long)i * a.g.rs + j) * 4u);
+    const Quad q = loss_quad(a.H, a.W);  // pixels outside the plane read 0 (an invalid target)
+    const f4 pv = load4_f32(a.p, a.H, a.W, q), gv = load4_f32(a.g, a.H, a.W, q);
     float s[kNS];
 #pragma unroll
     for (int k = 0; k < kNS; ++k) s[k] = 0.f;
@@ -72,41 +62,25 @@ __global__ __launch_bounds__(kMT) void metrics_partials(MetricsArgs a, float* __
     metrics_pixel(pv.z, gv.z, a, s);
     metrics_pixel(pv.w, gv.w, a, s);
 #pragma unroll
-    for (int k = 0; k < kNS; ++k)
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+    for (int k = 0; k < kNS; ++k) s[k] = wave_sum(s[k]);
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < kNS; ++k) red[w][k] = s[k];
     }
     __syncthreads();
-    if (threadIdx.x < kNS) {
-        const int k = threadIdx.x;
-        part[(size_t)blockIdx.x * kNS + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
+    if (threadIdx.x < kNS) part[(size_t)blockIdx.x * kNS + threadIdx.x] = waves_in_order(&red[0][threadIdx.x], kNS);
 }
 
-// One block. Wave w reduces images w, w + 16, ..: lane l adds tiles l, l + 64, .. in order (double),
-// then the xor tree over the lanes; the image's row goes to img (workspace) and to sums. After the
-// barrier thread k adds img[0..B)[k] in order into accum[k].
+// One block. Wave w reduces images w, w + 16, .. (image_tile_sums); the image's row goes to img
+// (workspace) and to sums. After the barrier thread k adds img[0..B)[k] in order into accum[k].
 __global__ __launch_bounds__(kFT) void metrics_finalize(const float* __restrict__ part, int B, int tiles,
                                                          double* __restrict__ img, double* __restrict__ sums,
                                                          double* __restrict__ accum) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int b = w; b < B; b += kFT / 64) {
-        const float* pb = part + (size_t)b * tiles * kNS;
         double s[kNS];
-#pragma unroll
-        for (int k = 0; k < kNS; ++k) s[k] = 0.0;
-        for (int t = lane; t < tiles; t += 64) {
-#pragma unroll
-            for (int k = 0; k < kNS; ++k) s[k] += (double)pb[(size_t)t * kNS + k];
-        }
-#pragma unroll
-        for (int k = 0; k < kNS; ++k)
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+        image_tile_sums(part + (size_t)b * tiles * kNS, tiles, lane, s);
         double mine = 0.0;  // lane k keeps sum k
 #pragma unroll
         for (int k = 0; k < kNS; ++k) mine = lane == k ? s[k] : mine;
@@ -125,11 +99,11 @@ __global__ __launch_bounds__(kFT) void metrics_finalize(const float* __restrict_
 }
 
 size_t metrics_workspace_bytes(int B, int H, int W) {
-    return (size_t)B * kNS * sizeof(double) + (size_t)B * metrics_tiles_per_image(H, W) * kNS * sizeof(float);
+    return (size_t)B * kNS * sizeof(double) + (size_t)B * loss_tiles_per_image(H, W) * kNS * sizeof(float);
 }
 
 int launch_metrics(const MetricsArgs& a, double* sums, double* accum, void* ws, hipStream_t st, const char** why) {
-    const int tiles = metrics_tiles_per_image(a.H, a.W);
+    const int tiles = loss_tiles_per_image(a.H, a.W);
     double* img = (double*)ws;
     float* part = (float*)(img + (size_t)a.B * kNS);
     hipLaunchKernelGGL(metrics_partials, dim3(a.B * tiles), dim3(kMT), 0, st, a, part);

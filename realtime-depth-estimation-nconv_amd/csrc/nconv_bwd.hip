@@ -18,15 +18,6 @@
 
 namespace nconv {
 
-static int last_err(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
-}
-
 static bool simple_geom(const nconv_layer& L) {
     return L.SH == 1 && L.SW == 1 && L.DH == 1 && L.DW == 1 && L.groups == 1 && L.KH == L.KW;
 }
@@ -211,7 +202,7 @@ int launch_bwd(const LayerDev& d, const BwdArgs& a, hipStream_t st, const char**
     // (dgrad_phase, the fused-tail layer's included, writes the upsampled half's gradient itself)
     if (is_upcat(L) && (a.gxb || a.gcb) && !(path == kTiled && dgrad_phase_ok(L)))
         launch_upsample_bwd_gather(d, a, tx, tc, st);
-    return last_err(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

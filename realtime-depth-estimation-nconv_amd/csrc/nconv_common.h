@@ -13,7 +13,8 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/nconv.h"
-#include "plane_io.h"  // f4, kOOB, plane_rsrc, ld_f32, launch_status
+#include "plane_io.h"  // f4, kOOB, plane_rsrc, ld_f32, PlaneView, the tile grid
+#include "wave_ops.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 

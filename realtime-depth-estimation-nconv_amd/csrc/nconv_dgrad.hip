@@ -242,20 +242,8 @@ __device__ void head_wgrad_epilogue(const LayerDev& d, const BwdArgs& a, int b, 
         sv[k] = in ? Sp[(size_t)qr * L.W + qc] : 0.f;
         cnt += sv[k] > a.hthresh ? 1 : 0;
     }
-    int incl = cnt;  // wave inclusive scan
-#pragma unroll
-    for (int sh = 1; sh < 64; sh <<= 1) {
-        const int t = __shfl_up(incl, sh);
-        if (lane >= sh) incl += t;
-    }
-    if (lane == 63) wtot[wv] = incl;
-    __syncthreads();
-    int off = incl - cnt, total = 0;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {
-        off += w2 < wv ? wtot[w2] : 0;
-        total += wtot[w2];
-    }
+    int total;
+    int off = block_excl_scan<4>(cnt, wtot, total);
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
         if (sv[k] > a.hthresh) {
@@ -264,15 +252,9 @@ __device__ void head_wgrad_epilogue(const LayerDev& d, const BwdArgs& a, int b, 
             ++off;
         }
     }
-    // dense sums: wave butterflies, then the four waves in order
+    // dense sums: wave_ops.h's order
 #pragma unroll
-    for (int i = 0; i < CIN; ++i) {
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) {
-            sgy[i] += __shfl_xor(sgy[i], sh);
-            sgc[i] += __shfl_xor(sgc[i], sh);
-        }
-    }
+    for (int i = 0; i < CIN; ++i) sgy[i] = wave_sum(sgy[i]), sgc[i] = wave_sum(sgc[i]);
     if (lane == 0)
 #pragma unroll
         for (int i = 0; i < CIN; ++i) {
@@ -305,7 +287,7 @@ __device__ void head_wgrad_epilogue(const LayerDev& d, const BwdArgs& a, int b, 
     tap_sums(0);
     if (tid >= kHeadNw && tid < kHeadNw + 2 * CIN) {
         const int k = tid - kHeadNw;
-        out[tid] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+        out[tid] = waves_in_order(&red[0][k], 2 * CIN);
     }
     if constexpr (NPL < CIN) {
         __syncthreads();  // every tap sum of the first half is done with its planes

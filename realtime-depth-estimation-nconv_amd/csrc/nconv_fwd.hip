@@ -366,15 +366,6 @@ __global__ __launch_bounds__(kPrepThreads) void weight_prep(PrepArgs a) {
 // ------------------------------------------------------------------------------------------------
 namespace nconv {
 
-static int last_launch(const char** why) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;  // EIO
-    }
-    return 0;
-}
-
 static bool simple_geometry(const nconv_layer& L) {
     return L.SH == 1 && L.SW == 1 && L.DH == 1 && L.DW == 1 && L.groups == 1 && L.KH == L.KW;
 }
@@ -437,8 +428,8 @@ int launch_fwd(const LayerDev& d, float* y, float* yc, float* py, float* pc, uns
     t.pc = pc;
     t.parg = parg;
     if (!parg) {  // the argmax codes are written by the tiled fp32 kernels only
-        if (launch_fwd_mfma(d, y, yc, t, false, st)) return last_launch(why);
-        if (launch_fwd_phase(d, y, yc, t, false, st)) return last_launch(why);
+        if (launch_fwd_mfma(d, y, yc, t, false, st)) return launch_status(why);
+        if (launch_fwd_phase(d, y, yc, t, false, st)) return launch_status(why);
     } else if (!fwd_tiled_shape(L) || L.math != NCONV_MATH_FP32) {
         *why = "pooling argmax codes need an exact-fp32 tiled layer (8->8 5x5, 1->8 5x5 threshold, 16->8 3x3)";
         return -95;
@@ -447,7 +438,7 @@ int launch_fwd(const LayerDev& d, float* y, float* yc, float* py, float* pc, uns
 #define NCONV_TRY(CIN, COUT, K, MODE)                                                       \
     if (L.Cin == CIN && L.Cout == COUT && L.KH == K && L.load_mode == MODE) {               \
         go_tiled<CIN, COUT, K, MODE, false>(d, y, yc, t, L.Ho, L.Wo, st);                   \
-        return last_launch(why);                                                             \
+        return launch_status(why);                                                             \
     }
         NCONV_TRY(1, 8, 5, NCONV_LOAD_THRESH)
         NCONV_TRY(8, 8, 5, NCONV_LOAD_PLAIN)
@@ -485,7 +476,7 @@ int launch_fwd(const LayerDev& d, float* y, float* yc, float* py, float* pc, uns
             *why = "unknown load mode";
             return -22;
     }
-    return last_launch(why);
+    return launch_status(why);
 }
 
 int launch_fwd_tail(const LayerDev& d, const TailArgs& t, float* out, hipStream_t st, const char** why) {
@@ -501,12 +492,12 @@ int launch_fwd_tail(const LayerDev& d, const TailArgs& t, float* out, hipStream_
             *why = "nconv6's outputs from the fused tail need the exact-fp32 phase form (exactly-2x upsampling, waux)";
             return -95;
         }
-        return last_launch(why);
+        return launch_status(why);
     }
-    if (launch_fwd_mfma(d, out, nullptr, t, true, st)) return last_launch(why);
-    if (launch_fwd_phase(d, out, nullptr, t, true, st)) return last_launch(why);
+    if (launch_fwd_mfma(d, out, nullptr, t, true, st)) return launch_status(why);
+    if (launch_fwd_phase(d, out, nullptr, t, true, st)) return launch_status(why);
     go_tiled<16, 8, 3, NCONV_LOAD_UPCAT_UP_FIRST, true>(d, out, nullptr, t, t.out_h, t.out_w, st);
-    return last_launch(why);
+    return launch_status(why);
 }
 
 int launch_weight_prep(int n, float* const* w, const int* cout, const int* fan_in, const int* sp,
@@ -525,7 +516,7 @@ int launch_weight_prep(int n, float* const* w, const int* cout, const int* fan_i
         a.softplus[i] = sp ? sp[i] : 0;
     }
     hipLaunchKernelGGL(weight_prep, dim3(n), dim3(kPrepThreads), 0, st, a);
-    return last_launch(why);
+    return launch_status(why);
 }
 
 }  // namespace nconv

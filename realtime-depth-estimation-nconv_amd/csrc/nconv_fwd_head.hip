@@ -451,8 +451,7 @@ __global__ __launch_bounds__(kPrepThreads) void weight_prologue(PrepArgs prep, i
         for (int r = 0; r < 8; ++r) {
             float sr = 0.f;
             if (lane < 25) sr += v[r];
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) sr += __shfl_xor(sr, m);
+            sr = wave_sum(sr);
             if ((lane & 7) == r) s1i = sr;
         }
         head_weights_unit(w1, s1i, w2, w21, unit, lane);
@@ -554,12 +553,7 @@ int launch_fwd_head_exact(const LayerDev& d2, const TailArgs& t, float* y, float
     dim3 grid(((L.Wo + kHTW - 1) / kHTW) * ((L.Ho + kHTH - 1) / kHTH) * L.B);  // see xcd_tile
     if (t.y1) hipLaunchKernelGGL(fwd_head_exact<true>, grid, dim3(kHT), 0, st, d2, t, y, yc);
     else hipLaunchKernelGGL(fwd_head_exact<false>, grid, dim3(kHT), 0, st, d2, t, y, yc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 int launch_weight_prologue(int n, float* const* w, const int* cout, const int* fan_in, float* const* s,
@@ -587,23 +581,13 @@ int launch_weight_prologue(int n, float* const* w, const int* cout, const int* f
     const int blocks = n + (w21 ? (kHeadUnits + 3) / 4 : 0) + nphase;
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(weight_prologue, dim3(blocks), dim3(kPrepThreads), 0, st, a, n, w1, w2, w21, p, nphase);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 int launch_head_weights(const float* w1, const float* s1, const float* w2, float* out, hipStream_t st,
                         const char** why) {
     hipLaunchKernelGGL(head_weights, dim3(kHeadUnits), dim3(64), 0, st, w1, s1, w2, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 int launch_train_prologue(int n, float* const* w, const int* cout, const int* fan_in, const int* sp,
@@ -648,12 +632,7 @@ int launch_train_prologue(int n, float* const* w, const int* cout, const int* fa
     static_assert(kTrainProThreads / 64 == 8, "a wave per nconv1 / nconv2 row");
     hipLaunchKernelGGL(train_prologue, dim3(blocks), dim3(kTrainProThreads), 0, st, a, nprep, w1, w2, s1, s2, sp1, sp2,
                        w21, sync, p, nphase);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 }  // namespace nconv

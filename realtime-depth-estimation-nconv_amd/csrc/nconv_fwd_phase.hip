@@ -351,12 +351,7 @@ int launch_phase_weights(int n, const float* const* w, const int* cin, const int
         a.cin[i] = cin[i];
     }
     hipLaunchKernelGGL(phase_weights, dim3(n), dim3(kPrepThreads), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
-    }
-    return 0;
+    return launch_status(why);
 }
 
 }  // namespace nconv

@@ -5,6 +5,16 @@
 
 namespace nconv {
 
+// after the launches of a host function: 0, or -EIO with *why = the runtime's message
+inline int launch_status(const char** why) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        *why = hipGetErrorString(e);
+        return -5;
+    }
+    return 0;
+}
+
 struct TailArgs {
     const float* w7;
     const float* b7;
@@ -218,19 +228,6 @@ int launch_relu_bias_bwd(int B, int C, int H, int W, const float* g, const float
                          float* ws, hipStream_t st, const char** why);
 int launch_bn_train_bwd(const nconv_bn_train& p, const float* gy, float* gx, float* ggamma, float* gbeta, float* ws,
                         hipStream_t st, const char** why);
-
-// A batch of B planes of H rows as the I/O kernels read it (plane_io.h); checked and filled by
-// view_args in capi_common.h. Strides are in the unit the owning struct states.
-struct PlaneView {
-    const void* base;
-    long long bs;  // image stride; 0 where B == 1
-    long long rs;  // row stride
-    int wide;      // base and strides keep every group of four pixels aligned for the wide loads
-    template <typename T>
-    __host__ __device__ const T* image(int b) const {
-        return (const T*)base + (long long)b * bs;
-    }
-};
 
 // Training loss (utils.py calculate_loss) on B planes.
 struct LossArgs {

@@ -20,7 +20,7 @@ struct PrepArgs {
 };
 
 // The normaliser of one weight row (step1.py:141-144) by one wave: lane-strided partial sums, then
-// a fixed-order xor butterfly (every lane ends with the same value).
+// wave_ops.h's wave_sum (every lane ends with the same value).
 __device__ __forceinline__ float row_sum_wave(const float* wr, int fan, int lane) {
     float s = 0.f;
     if (fan <= 256) {  // (every DNET layer) the lane's loads issued together, added in the same order
@@ -33,9 +33,7 @@ __device__ __forceinline__ float row_sum_wave(const float* wr, int fan, int lane
     } else {
         for (int i = lane; i < fan; i += 64) s += wr[i];
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
-    return s;
+    return wave_sum(s);
 }
 
 // EnforcePos's softplus of one weight, shared by every launch that applies it (weight_prep, the

@@ -323,15 +323,10 @@ __global__ __launch_bounds__(kWbT) void wgrad_bf(LayerDev d, BwdArgs a, float* p
             out[((o * CIN + i) * K + kh) * K + kw] = v;
         }
     }
-    // bias / wsum sums: each wave's channels, lanes combined in a fixed butterfly order
+    // bias / wsum sums: each wave's channels, lanes combined by wave_ops.h's wave_sum
 #pragma unroll
     for (int k = 0; k < C::OPW; ++k) {
-        float sb = gb_acc[k], ss = gs_acc[k];
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) {
-            sb += __shfl_xor(sb, sh);
-            ss += __shfl_xor(ss, sh);
-        }
+        const float sb = wave_sum(gb_acc[k]), ss = wave_sum(gs_acc[k]);
         if (lane == 0) {
             out[NW + w * C::OPW + k] = sb;
             out[NW + COUT + w * C::OPW + k] = ss;

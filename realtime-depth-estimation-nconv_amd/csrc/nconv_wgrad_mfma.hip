@@ -270,12 +270,8 @@ struct GRowStager {
 #pragma unroll
         for (int kk = 0; kk < OPW; ++kk) {
             const bool mine = hl && hkk == kk;  // the halo lanes' sums of this channel
-            float sb = gb_acc[kk] + (mine ? gb_h : 0.f), ss = gs_acc[kk] + (mine ? gs_h : 0.f);
-#pragma unroll
-            for (int sh = 32; sh > 0; sh >>= 1) {
-                sb += __shfl_xor(sb, sh);
-                ss += __shfl_xor(ss, sh);
-            }
+            const float sb = wave_sum(gb_acc[kk] + (mine ? gb_h : 0.f));
+            const float ss = wave_sum(gs_acc[kk] + (mine ? gs_h : 0.f));
             if (lane == 0) {
                 sums[w + 4 * kk] = sb;
                 sums[COUT + w + 4 * kk] = ss;
@@ -286,18 +282,12 @@ struct GRowStager {
 #pragma unroll
             for (int kk = 0; kk < OPW; ++kk) {
                 const bool mine = hl && hkk == kk;
-                float sn = w7n[kk] + (mine ? w7nh : 0.f), sd = w7d[kk] + (mine ? w7dh : 0.f);
-#pragma unroll
-                for (int sh = 32; sh > 0; sh >>= 1) {
-                    sn += __shfl_xor(sn, sh);
-                    sd += __shfl_xor(sd, sh);
-                }
+                const float sn = wave_sum(w7n[kk] + (mine ? w7nh : 0.f));
+                const float sd = wave_sum(w7d[kk] + (mine ? w7dh : 0.f));
                 if (lane == 0) o7[w + 4 * kk] = sn + sd;
             }
             if constexpr (GC7) {  // wave 0's sum: all four waves hold the same one (store()'s invariant)
-                float sg = gs7[0];
-#pragma unroll
-                for (int sh = 32; sh > 0; sh >>= 1) sg += __shfl_xor(sg, sh);
+                const float sg = wave_sum(gs7[0]);
                 if (threadIdx.x == 0) o7[8] = 0.f, o7[9] = sg;
             } else {
                 if (threadIdx.x < 2) o7[8 + threadIdx.x] = 0.f;

@@ -65,9 +65,8 @@ __global__ __launch_bounds__(kT) void occlusion_filter(OcclusionArgs a) {
     __shared__ unsigned s_n, s_nrm;
     const float kNone = __builtin_inff();
     const int tid = (int)threadIdx.x, lane = tid & 63;
-    const int ntw = (a.W + kTW - 1) / kTW, per = ntw * ((a.H + kTH - 1) / kTH);
-    const int b = blockIdx.x / per, t = blockIdx.x - b * per;
-    const int ti = (t / ntw) * kTH, tj = (t % ntw) * kTW;
+    const TileOrigin o = tile_origin<kTH, kTW>(a.H, a.W);
+    const int b = o.b, ti = o.i0, tj = o.j0;
     const int rh = a.rh, rw = a.rw, rwp = (rw + 3) & ~3;  // the staged columns start at tj - rwp
     const __amdgpu_buffer_rsrc_t r = plane_rsrc(a.s.image<float>(b), view_bytes(a.H, a.s.rs, a.W, 4));
     const bool wide = a.s.wide != 0;
@@ -192,7 +191,7 @@ int launch_depth_occlusion(const OcclusionArgs& a, hipStream_t st, const char** 
         const unsigned n = 2u * (unsigned)a.B;
         hipLaunchKernelGGL(occlusion_counts_reset, dim3((n - 1) / kT + 1), dim3(kT), 0, st, a.counts, n);
     }
-    const long long tiles = (long long)((a.H + kTH - 1) / kTH) * ((a.W + kTW - 1) / kTW);
+    const long long tiles = tiles_per_image<kTH, kTW>(a.H, a.W);
     hipLaunchKernelGGL(occlusion_filter, dim3((unsigned)(a.B * tiles)), dim3(kT), 0, st, a);  // <= B * H * W < 2^31
     return launch_status(why);
 }

@@ -1,9 +1,12 @@
-// plane_io.h — reading a strided view of 2-D planes on the device, defined once for the I/O kernels
-// (metrics.hip, frame_io.hip, backproject.hip; loss.hip and lidar_project.hip take the constants).
+// plane_io.h — reading a strided view of 2-D planes on the device, and the grid of pixel tiles the
+// kernels over such planes are launched on, defined once. Every kernel that takes a PlaneView reads it
+// through these loaders (the loss, confidence-loss and metrics kernels, frame_io, backproject, normals,
+// colorize, occlusion, ipbasic, nearest, augment, view_warp); the NConv staging (nconv_common.h) and
+// lidar_project.hip take the resource constants and ld_f32.
 //
-// A view is a batch of planes given as (base, image stride, row stride): PlaneView in
-// nconv_internal.h, checked and filled on the host by view_args in capi_common.h. A kernel reads
-// image b through a buffer resource over exactly that image's extent,
+// A view is a batch of planes given as (base, image stride, row stride): PlaneView below, checked and
+// filled on the host by view_args in capi_common.h. A kernel reads image b through a buffer resource
+// over exactly that image's extent,
 //   [base + b * image stride, + ((H - 1) * row stride + row elements) * element bytes),
 // which the host keeps below 2^31 bytes, so that the byte offset kOOB lies past every resource and a
 // load aimed at it returns 0 without touching memory. A lane takes four consecutive pixels of one
@@ -79,12 +82,74 @@ __device__ __forceinline__ void store4_f32(float* p, f4 v, int n) {
     if (n > 3) p[3] = v.w;
 }
 
-// after the launches of a host function: 0, or -EIO with *why = the runtime's message
-inline int launch_status(const char** why) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        *why = hipGetErrorString(e);
-        return -5;
+namespace nconv {
+
+// A batch of B planes of H rows; checked and filled by view_args in capi_common.h. Strides are in the
+// unit the owning struct states.
+struct PlaneView {
+    const void* base;
+    long long bs;  // image stride; 0 where B == 1
+    long long rs;  // row stride
+    int wide;      // base and strides keep every group of four pixels aligned for the wide loads
+    template <typename T>
+    __host__ __device__ const T* image(int b) const {
+        return (const T*)base + (long long)b * bs;
     }
-    return 0;
+};
+
+// The pixel-tile grid: a plane is cut into tiles of TH x TW pixels, row-major; a 1-D grid takes the
+// tiles of image 0, then image 1, ..: one workgroup per tile.
+template <int TH, int TW>
+__host__ __device__ __forceinline__ int tiles_per_image(int H, int W) {
+    return ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
 }
+// first row and column of tile t of an image
+template <int TH, int TW>
+__device__ __forceinline__ void tile_corner(int W, int t, int& i0, int& j0) {
+    const int ntw = (W + TW - 1) / TW;
+    i0 = (t / ntw) * TH, j0 = (t % ntw) * TW;
+}
+struct TileOrigin {
+    int b, i0, j0;  // image; the tile's first row and column
+};
+// the tile of this workgroup
+template <int TH, int TW>
+__device__ __forceinline__ TileOrigin tile_origin(int H, int W) {
+    const int per = tiles_per_image<TH, TW>(H, W);
+    TileOrigin o;
+    o.b = blockIdx.x / per;
+    tile_corner<TH, TW>(W, blockIdx.x - o.b * per, o.i0, o.j0);
+    return o;
+}
+
+// The 16 x 64 tile of the loss family (loss.hip, conf_loss.hip, metrics.hip, view_warp.hip): 1024
+// pixels, four per thread of a 256-thread workgroup.
+constexpr int kLossTH = 16, kLossTW = 64;
+__host__ __device__ __forceinline__ int loss_tiles_per_image(int H, int W) {
+    return tiles_per_image<kLossTH, kLossTW>(H, W);
+}
+
+// That tile with four consecutive pixels of a row per thread (conf_loss.hip, metrics.hip): thread t
+// owns row t >> 4, columns 4 (t & 15) .. + 3.
+struct Quad {
+    int b, i, j, n;  // image; the thread's row and first column; how many of its four pixels are in the row
+    bool row_in;
+};
+__device__ __forceinline__ Quad loss_quad(int H, int W) {
+    const TileOrigin o = tile_origin<kLossTH, kLossTW>(H, W);
+    Quad q;
+    q.b = o.b;
+    q.i = o.i0 + (threadIdx.x >> 4);
+    q.j = o.j0 + (threadIdx.x & 15) * 4;
+    q.row_in = q.i < H;
+    q.n = min(4, W - q.j);
+    return q;
+}
+// the thread's four pixels of an fp32 view (strides in elements); pixels outside the plane read 0
+using ::load4_f32;
+__device__ __forceinline__ f4 load4_f32(const PlaneView& p, int H, int W, const Quad& q) {
+    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(p.image<float>(q.b), view_bytes(H, p.rs, W, 4));
+    return load4_f32(rs, p.wide != 0, q.row_in, q.n, (unsigned)((long long)q.i * p.rs + q.j) * 4u);
+}
+
+}  // namespace nconv

@@ -94,43 +94,21 @@ __device__ __forceinline__ float plane_at(const PlaneView& v, int b, unsigned ro
     return v.image<float>(b)[(long long)row * v.rs + col];
 }
 
-// exclusive prefix of v over the workgroup's threads in thread order, and the total
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned& total) {
+// exclusive prefix of v over the workgroup's threads in thread order, and the total (wave_ops.h); a
+// kernel's calls share s_wave
+__device__ __forceinline__ unsigned excl_scan(unsigned v, unsigned& total) {
     __shared__ unsigned s_wave[kT / 64];
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();  // s_wave of an earlier call has been read
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kT / 64; ++i) {
-        if (i < wave) base += s_wave[i];
-        total += s_wave[i];
-    }
-    return base + inc - v;
+    return block_excl_scan<kT / 64, unsigned, true>(v, s_wave, total);
 }
 
-// The fixed summation tree of kT doubles (twice): inside a wave lanes l and l ^ 32, then ^ 16, .. ^ 1;
-// then ((wave 0 + wave 1) + wave 2) + wave 3. Every thread returns with the totals.
+// wave_ops.h's tree over kT doubles, twice behind one barrier. Every thread returns with the totals.
 __device__ __forceinline__ void block_sum2(double& x, double& y) {
     __shared__ double s_x[kT / 64], s_y[kT / 64];
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        x += __shfl_xor(x, m);
-        y += __shfl_xor(y, m);
-    }
+    x = wave_sum(x), y = wave_sum(y);
     if (lane == 0) s_x[wave] = x, s_y[wave] = y;
     __syncthreads();
-    x = ((s_x[0] + s_x[1]) + s_x[2]) + s_x[3];
-    y = ((s_y[0] + s_y[1]) + s_y[2]) + s_y[3];
+    x = waves_in_order(s_x), y = waves_in_order(s_y);
 }
 
 __global__ __launch_bounds__(kT) void spars_count(SparsificationArgs A, unsigned* __restrict__ tilecnt, int ntiles) {
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(kT) void spars_count(SparsificationArgs A, unsigned
         }
     }
     unsigned total;
-    block_excl_scan(c, total);
+    excl_scan(c, total);
     if (threadIdx.x == 0) tilecnt[blockIdx.x] = total;
 }
 
@@ -163,8 +141,8 @@ __global__ __launch_bounds__(kT) void spars_prepare(SparsificationArgs A, Buffer
         bef += i < tile ? v : 0u;
     }
     unsigned before, nb, tmp;
-    block_excl_scan(bef, before);  // the totals are all this needs
-    block_excl_scan(all, nb);
+    excl_scan(bef, before);  // the totals are all this needs
+    excl_scan(all, nb);
     if (tile == 0 && threadIdx.x == 0) w.nvalid[b] = (int)nb;
 
     const unsigned p0 = (unsigned)tile * kPrepTile + threadIdx.x * kPrepPix;
@@ -191,7 +169,7 @@ __global__ __launch_bounds__(kT) void spars_prepare(SparsificationArgs A, Buffer
         w.tq[(size_t)b * hw + p] = q;
         mask |= 1u << k, ++c;
     }
-    unsigned r = before + block_excl_scan(c, tmp);
+    unsigned r = before + excl_scan(c, tmp);
     const size_t s0 = (size_t)(2 * b) * hw, s1 = s0 + hw;
 #pragma unroll
     for (int k = 0; k < kPrepPix; ++k) {
@@ -250,7 +228,7 @@ __global__ __launch_bounds__(kT) void spars_scatter(const unsigned* __restrict__
         before += i < blk ? v : 0u;
     }
     unsigned total;
-    unsigned run = block_excl_scan(all, total) + before;  // its barriers also cover s_wcnt's zeroes
+    unsigned run = excl_scan(all, total) + before;  // its barriers also cover s_wcnt's zeroes
     const size_t sb = (size_t)seg * hw;
     for (long long r0 = lo; r0 < hi; r0 += kTile) {
         const long long i = r0 + tid;

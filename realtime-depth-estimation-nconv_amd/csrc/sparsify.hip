@@ -92,27 +92,14 @@ __device__ __forceinline__ int target_of(const SparsifyArgs& a, int b, unsigned 
 // the state after digit jp - 1 in the workspace (written during an earlier kernel).
 __device__ SparsifySel resolve(const SparsifyArgs& a, int jp, int b) {
     __shared__ unsigned s_wave[kT / 64], s_digit, s_before;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const unsigned* h = a.hist + ((size_t)jp * a.B + b) * kBins + tid * (kBins / kT);
     unsigned v[kBins / kT], sum = 0;
 #pragma unroll
     for (int k = 0; k < kBins / kT; ++k) v[k] = h[k], sum += v[k];
-    unsigned inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    if (tid == 0) s_digit = 0u, s_before = 0u;
-    __syncthreads();
-    unsigned base = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < kT / 64; ++i) {
-        if (i < wave) base += s_wave[i];
-        total += s_wave[i];
-    }
-    const unsigned excl = base + inc - sum;
+    if (tid == 0) s_digit = 0u, s_before = 0u;  // the scan's barrier covers these too
+    unsigned total;
+    const unsigned excl = block_excl_scan<kT / 64>(sum, s_wave, total);
     SparsifySel s;
     if (jp == 0) {
         s.n = target_of(a, b, total);

@@ -25,9 +25,9 @@
 //   view_warp_fwd        warped (B, C, H, W) and / or valid (B, H, W)
 //   view_warp_bwd        g_depth from g_warped
 //   photo_partials       per tile: the fp32 sum of its 1024 terms sum_ch |s - tgt| (a thread's four in row
-//                        order, the xor tree over the lanes, the four waves in order) and its valid count
-//   photo_finalize       one block: a wave per image sums its tiles in a fixed order (double; the counts
-//                        in integers), thread 0 adds the images in order and writes n_v and L
+//                        order, then wave_ops.h's wave_sum and waves_in_order) and its valid count
+//   photo_finalize       one block: a wave per image sums its tiles (image_tile_sums; the counts in
+//                        integers), thread 0 adds the images in order and writes n_v and L
 //   photo_grad           g_depth with g_s = kk sign(s - tgt), kk from the device's n_v: neither warped
 //                        nor g_s reaches memory
 //
@@ -41,11 +41,8 @@ namespace nconv {
 namespace {
 
 constexpr int kWT = 256;               // threads: four waves
-constexpr int kWH = 16, kWW = 64;      // pixel tile of one workgroup
-constexpr int kWRows = kWH / (kWT / 64);  // rows of the tile per thread
+constexpr int kWRows = kLossTH / (kWT / 64);  // rows of the tile (plane_io.h's 16 x 64) per thread
 constexpr int kWF = 1024;              // finalize: sixteen waves, one image each at a time
-
-int warp_tiles_per_image(int H, int W) { return ((H + kWH - 1) / kWH) * ((W + kWW - 1) / kWW); }
 
 // the photometric loss's workspace: n_v first (the backward and the caller read it there)
 struct PhotoWs {
@@ -94,13 +91,8 @@ struct WarpTile {
     int b, i0, j;
 };
 __device__ __forceinline__ WarpTile warp_tile(const WarpArgs& a) {
-    const int ntw = (a.W + kWW - 1) / kWW, nth = (a.H + kWH - 1) / kWH;
-    WarpTile t;
-    t.b = blockIdx.x / (ntw * nth);
-    const int k = blockIdx.x - t.b * ntw * nth;
-    t.i0 = (k / ntw) * kWH + (int)(threadIdx.x >> 6);
-    t.j = (k % ntw) * kWW + (int)(threadIdx.x & 63);
-    return t;
+    const TileOrigin o = tile_origin<kLossTH, kLossTW>(a.H, a.W);
+    return WarpTile{o.b, o.i0 + (int)(threadIdx.x >> 6), o.j0 + (int)(threadIdx.x & 63)};
 }
 
 // the projection of one target pixel: validity, the coordinates, the weights and the taps' byte offsets
@@ -282,39 +274,28 @@ __global__ __launch_bounds__(kWT) void photo_partials(WarpArgs a, float* __restr
         s += g.ok ? term : 0.f;
         n += g.ok ? 1 : 0;
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        s += __shfl_xor(s, m);
-        n += __shfl_xor(n, m);
-    }
+    s = wave_sum(s), n = wave_sum(n);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s, redc[threadIdx.x >> 6] = n;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-        cnt[blockIdx.x] = ((redc[0] + redc[1]) + redc[2]) + redc[3];
-    }
+    if (threadIdx.x == 0) part[blockIdx.x] = waves_in_order(red), cnt[blockIdx.x] = waves_in_order(redc);
 }
 
-// One block. Wave w reduces images w, w + 16, ..: lane l adds tiles l, l + 64, .. in order (double; the
-// counts in integers), then the xor tree over the lanes. After the barrier thread 0 adds the images in
-// order and writes n_v and L = (sum) / ((float)C * (float)max(n_v, 1)).
+// One block. Wave w reduces images w, w + 16, .. (image_tile_sums; the counts likewise in integers).
+// After the barrier thread 0 adds the images in order and writes n_v and
+// L = (sum) / ((float)C * (float)max(n_v, 1)).
 __global__ __launch_bounds__(kWF) void photo_finalize(const float* __restrict__ part, const int* __restrict__ cnt,
                                                       int B, int tiles, int C, double* __restrict__ img,
                                                       int* __restrict__ icnt, int* __restrict__ n_v,
                                                       float* __restrict__ loss) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int b = w; b < B; b += kWF / 64) {
-        const float* pb = part + (size_t)b * tiles;
         const int* cb = cnt + (size_t)b * tiles;
-        double s = 0.0;
+        double s[1];
+        image_tile_sums(part + (size_t)b * tiles, tiles, lane, s);
         int n = 0;
-        for (int t = lane; t < tiles; t += 64) s += (double)pb[t], n += cb[t];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            s += __shfl_xor(s, m);
-            n += __shfl_xor(n, m);
-        }
-        if (lane == 0) img[b] = s, icnt[b] = n;
+        for (int t = lane; t < tiles; t += 64) n += cb[t];
+        n = wave_sum(n);
+        if (lane == 0) img[b] = s[0], icnt[b] = n;
     }
     __syncthreads();  // img and icnt written by this block's waves
     if (threadIdx.x == 0) {
@@ -364,11 +345,11 @@ __global__ __launch_bounds__(kWT) void photo_grad(WarpArgs a, const float* __res
 
 size_t photo_loss_workspace_bytes(int B, int H, int W) {
     // photo_ws: n_v and padding, img, icnt (an even number of ints), part, cnt
-    return 8 + (size_t)B * 8 + (size_t)(B + (B & 1)) * 4 + (size_t)B * warp_tiles_per_image(H, W) * 8;
+    return 8 + (size_t)B * 8 + (size_t)(B + (B & 1)) * 4 + (size_t)B * loss_tiles_per_image(H, W) * 8;
 }
 
 int launch_view_warp_fwd(const WarpArgs& a, float* warped, unsigned char* valid, hipStream_t st, const char** why) {
-    const dim3 g(a.B * warp_tiles_per_image(a.H, a.W)), t(kWT);
+    const dim3 g(a.B * loss_tiles_per_image(a.H, a.W)), t(kWT);
     if (a.C == 1)
         hipLaunchKernelGGL(view_warp_fwd<1>, g, t, 0, st, a, warped, valid);
     else
@@ -377,7 +358,7 @@ int launch_view_warp_fwd(const WarpArgs& a, float* warped, unsigned char* valid,
 }
 
 int launch_view_warp_bwd(const WarpArgs& a, const float* g_warped, float* g_depth, hipStream_t st, const char** why) {
-    const dim3 g(a.B * warp_tiles_per_image(a.H, a.W)), t(kWT);
+    const dim3 g(a.B * loss_tiles_per_image(a.H, a.W)), t(kWT);
     if (a.C == 1)
         hipLaunchKernelGGL(view_warp_bwd<1>, g, t, 0, st, a, g_warped, g_depth);
     else
@@ -386,7 +367,7 @@ int launch_view_warp_bwd(const WarpArgs& a, const float* g_warped, float* g_dept
 }
 
 int launch_photo_loss_fwd(const WarpArgs& a, float* loss, void* ws, hipStream_t st, const char** why) {
-    const int tiles = warp_tiles_per_image(a.H, a.W);
+    const int tiles = loss_tiles_per_image(a.H, a.W);
     const PhotoWs p = photo_ws(ws, a.B, tiles);
     const dim3 g(a.B * tiles), t(kWT);
     if (a.C == 1)
@@ -400,7 +381,7 @@ int launch_photo_loss_fwd(const WarpArgs& a, float* loss, void* ws, hipStream_t 
 
 int launch_photo_loss_bwd(const WarpArgs& a, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
                           const char** why) {
-    const dim3 g(a.B * warp_tiles_per_image(a.H, a.W)), t(kWT);
+    const dim3 g(a.B * loss_tiles_per_image(a.H, a.W)), t(kWT);
     const int* n_v = (const int*)ws;
     if (a.C == 1)
         hipLaunchKernelGGL(photo_grad<1>, g, t, 0, st, a, gloss, n_v, g_depth);

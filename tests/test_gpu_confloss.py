@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import confloss_cases as CC
+import reduce_tree as RT
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +43,21 @@ def test_conf_loss_matches_rule(nconv_amd, gpu, H, W, err, beta, lam):
         r = torch.tensor([3.25, 9.0]).reshape(2, 1, 1, 1)
         c = torch.tensor([1.0, 0.5]).reshape(2, 1, 1, 1)
     _check(nconv_amd, r.to(gpu), c.to(gpu), t.to(gpu), lam, err, beta)
+
+
+@pytest.mark.parametrize("shape", [(3, 33, 70), (17, 17, 65)], ids=["3x33x70", "17x17x65"])
+def test_conf_loss_sum_is_the_stated_tree(nconv_amd, gpu, shape):
+    """L bit for bit from the rule's fp32 terms summed in the order csrc/wave_ops.h states (reduce_tree.py,
+    conf_loss.hip's thread map): partial tiles in both directions and six tiles per image; seventeen
+    images, so that a wave of the finalize stage takes a second one."""
+    B, H, W = shape
+    g = torch.Generator().manual_seed(1000 * B + W)
+    r, c, t = CC.loss_inputs(g, (B, 1, H, W))
+    L = nconv_amd.confidence_loss(r.to(gpu), t.to(gpu), c.to(gpu), 0.5)
+    terms, _, _ = CC.rule_fp32(r.numpy(), c.numpy(), t.numpy(), 0.5)
+    want = RT.loss(terms.reshape(B, H, W), float(B * H * W), RT.QUAD)
+    print(f"L {L.item():.9g} tree {want:.9g}")
+    assert RT.same_bits(L.item(), want)
 
 
 @pytest.mark.parametrize("err", ["smooth_l1", "l2"])

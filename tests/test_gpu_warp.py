@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import reduce_tree as RT
 import warp_cases as WC
 from test_gpu_dnet import sparse_depth
 
@@ -63,6 +64,22 @@ def test_warp_and_loss_match_rule(nconv_amd, gpu, size, src_size, C, per_image_m
     x = WC.warp_inputs(100 * size[0] + size[1] + C, 2, C, size, src_size, per_image_m, with_mask=(C == 1))
     (_, valid, *_), rule = _check(nconv_amd, x, _dev(x, gpu))
     assert 0 < rule["n_v"] < valid.numel()  # both kinds of pixel took part
+
+
+@pytest.mark.parametrize("shape", [(3, 33, 70), (17, 17, 65)], ids=["3x33x70", "17x17x65"])
+def test_photo_loss_sum_is_the_stated_tree(nconv_amd, gpu, shape):
+    """L bit for bit from the rule's fp32 terms summed in the order csrc/wave_ops.h states (reduce_tree.py,
+    view_warp.hip's thread map): partial tiles in both directions and six tiles per image; seventeen
+    images, so that a wave of the finalize stage takes a second one."""
+    B, H, W = shape
+    x = WC.warp_inputs(1000 * B + W, B, 3, (H, W), None, True, with_mask=False)
+    t = _dev(x, gpu)
+    L, n_v = nconv_amd.photometric_loss(t["depth"], t["k"], t["tgt"], t["src"], t["m"], return_valid_count=True)
+    rule = WC.rule_fp32(x["depth"], x["k"], x["src"], x["m"], None, x["tgt"])
+    want = RT.loss(rule["terms"], float(rule["den"]), RT.ROWS)
+    print(f"L {L.item():.9g} tree {want:.9g} n_v {n_v.item()}")
+    assert n_v.item() == rule["n_v"] and 0 < rule["n_v"] < B * H * W
+    assert RT.same_bits(L.item(), want)
 
 
 @pytest.mark.parametrize("C", [1, 3])
