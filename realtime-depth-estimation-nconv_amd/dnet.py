@@ -26,9 +26,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, _streams, export, nconv
-from .nconv import (EnforcePos, NConv2d, WgradReduce, _require_device, head_weights, layer_backward,
-                    layer_forward_head, layer_forward_pooled, layer_forward_raw, nconv_layer, phase_weights,
-                    train_prologue, weight_prep)
+from .nconv import (EnforcePos, HeadBwd, InputGrads, NConv2d, Operands, PoolGrad, TailBwd, WgradReduce,
+                    _require_device, head_weights, layer_backward, layer_forward_head, layer_forward_pooled,
+                    layer_forward_raw, nconv_layer, phase_weights, train_prologue, weight_prep)
 
 LAYERS = ("nconv1", "nconv2", "nconv_down1", "nconv_down2", "nconv_down3", "nconv4", "nconv5",
           "nconv6", "nconv7")
@@ -114,10 +114,62 @@ def _batch_rows(full, B, b0, b1):
     return rows
 
 
+class TrainActs(NamedTuple):
+    """What DNETFn's forward keeps for its backward, in the order it is saved: the nine layers'
+    outputs (x, c) in LAYERS order, then (pooled graph only) the 2x2-pooled copies of nconv2's,
+    down1's and down2's outputs (p2, p3, p4) with their pooling argmax codes (a2, a3, a4)."""
+    x1: torch.Tensor
+    c1: torch.Tensor
+    x2: torch.Tensor
+    c2: torch.Tensor
+    x3: torch.Tensor
+    c3: torch.Tensor
+    x4: torch.Tensor
+    c4: torch.Tensor
+    x5: torch.Tensor
+    c5: torch.Tensor
+    x6: torch.Tensor
+    c6: torch.Tensor
+    x7: torch.Tensor
+    c7: torch.Tensor
+    x8: torch.Tensor
+    c8: torch.Tensor
+    x9: torch.Tensor
+    c9: torch.Tensor
+    p2x: Optional[torch.Tensor] = None
+    p2c: Optional[torch.Tensor] = None
+    a2: Optional[torch.Tensor] = None
+    p3x: Optional[torch.Tensor] = None
+    p3c: Optional[torch.Tensor] = None
+    a3: Optional[torch.Tensor] = None
+    p4x: Optional[torch.Tensor] = None
+    p4c: Optional[torch.Tensor] = None
+    a4: Optional[torch.Tensor] = None
+
+    def flatten(self):  # 18 tensors, or 27 with the pooled graph's: what save_for_backward takes
+        return tuple(self) if self.p2x is not None else tuple(self)[:18]
+
+    def outputs(self):  # the nine layers' (x, c)
+        return tuple(zip(self[0:18:2], self[1:18:2]))
+
+
+class _BwdLayer(NamedTuple):
+    """One layer in DNETFn.backward: its spec and (weight, bias, s[o]), and where its weight and
+    bias gradients go (None: not needed)."""
+    spec: nconv.LayerSpec
+    weight: torch.Tensor
+    bias: torch.Tensor
+    wsum: torch.Tensor
+    gw: Optional[torch.Tensor]
+    gb: Optional[torch.Tensor]
+
+    def operands(self, a, b=(None, None)):  # a, b: the (x, c) pairs the layer reads
+        return Operands(*a, *b, self.weight, self.bias, self.wsum)
+
+
 def _train_fwd_chain(sp, W, S, w21, wph, crop, out, pooled=True):
     """DNETFn's forward launches over S's frames; out: None (fresh tensors) or a callable handing
-    out each launch's output tensors (nconv._outputs). Returns x1, c1, ..., x9, c9, then the pooled
-    copies and argmax codes (pooled graph)."""
+    out each launch's output tensors (nconv._outputs). Returns the TrainActs."""
     w4, w5, w6 = (None, None, None) if wph is None else tuple(wph)
     if pooled:
         spp = [dataclasses.replace(sp[k], mode=_lib.PLAIN) for k in (2, 3, 4)]
@@ -149,7 +201,7 @@ def _train_fwd_chain(sp, W, S, w21, wph, crop, out, pooled=True):
     else:
         x8, c8 = layer_forward_raw(sp[7], x2, c2, x7, c7, *W[7], out=out, wphase=w6)
         x9, c9 = layer_forward_raw(sp[8], x8, c8, None, None, *W[8], out=out)
-    return (x1, c1, x2, c2, x3, c3, x4, c4, x5, c5, x6, c6, x7, c7, x8, c8, x9, c9, *pools)
+    return TrainActs(x1, c1, x2, c2, x3, c3, x4, c4, x5, c5, x6, c6, x7, c7, x8, c8, x9, c9, *pools)
 
 
 class DNETFn(torch.autograd.Function):
@@ -202,128 +254,123 @@ class DNETFn(torch.autograd.Function):
                 return r if b0 == 0 else None
             res = _streams.fork_join("train_fwd", S.device, [B * k // nst for k in range(nst + 1)], chain)[0]
             base = {t.data_ptr(): t for t in full}
-            acts = [base[t.data_ptr()] for t in res]
+            acts = TrainActs(*[base[t.data_ptr()] for t in res])
         else:
             acts = _train_fwd_chain(sp, W, S, w21, wph, crop, None, pooled=pooled)
-        # acts: (x, c) of the nine layers' outputs, then the pooled copies and argmax codes
         if capture is not None:  # the three pooling stages' inputs (DNET.capture)
-            capture.update(down1=(acts[2].detach(), acts[3].detach()), down2=(acts[4].detach(), acts[5].detach()),
-                           down3=(acts[6].detach(), acts[7].detach()))
+            capture.update(down1=(acts.x2.detach(), acts.c2.detach()), down2=(acts.x3.detach(), acts.c3.detach()),
+                           down3=(acts.x4.detach(), acts.c4.detach()))
         ctx.specs = specs
         ctx.pooled = pooled
-        ctx.save_for_backward(S, *p[:27], *acts)
-        x9, c9 = acts[16], acts[17]
+        ctx.save_for_backward(S, *p[:3 * len(LAYERS)], *acts.flatten())
         if not train_conf:
-            ctx.mark_non_differentiable(c9)
+            ctx.mark_non_differentiable(acts.c9)
         ctx.set_materialize_grads(False)  # no zero-filled gradient for a c9 (or x9) that is never used
-        return x9, c9
+        return acts.x9, acts.c9
 
     @staticmethod
     def backward(ctx, g9, gc9):
-        S, *sv = ctx.saved_tensors
-        W = [sv[3 * i:3 * i + 3] for i in range(9)]          # (weight, bias, s[o]) per layer
-        acts, pools = sv[27:45], sv[45:]                      # the layers' (x, c); the pooled graph's extras
-        X = [None] + [(acts[2 * i], acts[2 * i + 1]) for i in range(9)]  # X[k] = output of layer k
+        S, *saved = ctx.saved_tensors
+        nw = 3 * len(LAYERS)
+        A = TrainActs(*saved[nw:])
+        y1, y2, yd1, yd2, yd3, y4, y5, y6, y7 = A.outputs()  # each layer's output (x, c), by layer
         if g9 is None:  # (grads are not materialised)
-            g9 = torch.zeros_like(X[9][0])
+            g9 = torch.zeros_like(A.x9)
         if gc9 is not None:  # (DNETConfFn only; the unfused branch hands it to nconv7's general backward)
             gc9 = gc9.contiguous()
-        wbox = (None, None, None) if ctx.wbox is None else tuple(ctx.wbox)
+        box4, box5, box6 = (None, None, None) if ctx.wbox is None else tuple(ctx.wbox)
         need_S, *need = ctx.needs_input_grad[3:]  # (after specs, capture, crop: S, then w1, b1, s1, w2, ...)
-        gw = [torch.empty_like(W[i][0]) if need[3 * i] else None for i in range(9)]
-        gb = [torch.empty_like(W[i][1]) if need[3 * i + 1] else None for i in range(9)]
-        e = torch.empty_like
-        # input gradients: G[k] = (gx, gc) of layer k's output
-        G = [None] * 10
-        sp = ctx.specs
+        e, none = torch.empty_like, (None, None)
+        grad_of = lambda y: (e(y[0]), e(y[1]))  # noqa: E731  an (x, c) pair's gradient (gx, gc), to be overwritten
+        layers = [_BwdLayer(sp, w, b, s, e(w) if need[3 * i] else None, e(b) if need[3 * i + 1] else None)
+                  for i, (sp, (w, b, s)) in enumerate(zip(ctx.specs, DNETArgs.unflatten(saved[:nw]).layers))]
+        n1, n2, d1, d2, d3, n4, n5, n6, n7 = layers
+        pooled = ctx.pooled
         red = WgradReduce()  # every layer's weight-gradient reduction in two launches at the end
-        side = _streams.SideStream("dnet_wgrad", S.device) if (ctx.pooled and WGRAD_STREAM) else None
+        side = _streams.SideStream("dnet_wgrad", S.device) if (pooled and WGRAD_STREAM) else None
 
-        def layer_bwd(spec, inputs, y, co, gy, gco, gin, gw_, gb_, **kw):
+        def split(spec, inputs, y, co, gy, gco, gin, gw, gb, head=None, tail=None, **kw):
             # the weight gradient runs on the side stream, concurrent with this layer's input gradient
             # (and the next layers' input gradients, which do not depend on it): it needs only tensors
             # that are complete when this layer's backward starts
-            if side is None or (gw_ is None and gb_ is None):
-                layer_backward(spec, inputs, y, co, gy, gco, gin, gw_, gb_, defer=red, **kw)
+            if side is None or (gw is None and gb is None):
+                layer_backward(spec, inputs, y, co, gy, gco, gin, gw, gb, defer=red, head=head, tail=tail, **kw)
                 return
             st = side.fork()
-            tail, head = kw.pop("tail", None), kw.pop("head", None)
             layer_backward(spec, inputs, y, co, gy, gco, gin, None, None, defer=red, head=head,
-                           tail=None if tail is None else tail[:7] + (None,) + tail[8:], **kw)  # (no gw7)
+                           tail=None if tail is None else tail._replace(gw=None), **kw)  # (no gw7)
             with torch.cuda.stream(st):
-                layer_backward(spec, inputs, y, co, gy, gco, (None,) * 4, gw_, gb_, defer=red, tail=tail, **kw)
+                layer_backward(spec, inputs, y, co, gy, gco, InputGrads(), gw, gb, defer=red, tail=tail, **kw)
 
-        def bwd(k, a, b, ga, gb_, acc=False, src_a=None, spec=None, pool_grad=None, box=None):
-            xa, ca = src_a if src_a is not None else (X[a] if a else (S, None))
-            xb, cb = X[b] if b else (None, None)
-            gy, gco = G[k] if G[k] is not None else (g9, gc9)
-            layer_bwd(spec or sp[k - 1], (xa, ca, xb, cb, *W[k - 1]), X[k][0], X[k][1], gy, gco,
-                      (*(ga or (None, None)), *(gb_ or (None, None))), gw[k - 1], gb[k - 1], accumulate=acc,
-                      pool_grad=pool_grad, box=box)
+        def bwd(layer, a, b, out, gout, into_a, into_b, spec=None, **kw):
+            # `layer` read the (x, c) pairs a and b and wrote out, whose gradient is gout; a's and b's gradients
+            # go into the pairs into_a and into_b
+            split(spec or layer.spec, layer.operands(a, b), *out, *gout, InputGrads(*into_a, *into_b), layer.gw,
+                  layer.gb, **kw)
 
-        G[2], G[7] = (e(X[2][0]), e(X[2][1])), (e(X[7][0]), e(X[7][1]))
+        # -- tail: nconv7, nconv6 --
+        g2, g5 = grad_of(y2), grad_of(y5)
         # (nconv7's weight gradient is accumulated inside nconv6's weight-gradient pass, so the fused
         # form needs nconv6's gw or gb too; gc9, the output confidence's gradient, is None unless a
         # confidence loss was applied to forward_with_confidence's pair)
-        if ctx.crop is not None or (FUSE_TAIL_BWD and ctx.pooled and _exact_up(*S.shape[2:]) and gw[8] is not None
-                                    and (gw[7] is not None or gb[7] is not None)):
+        if ctx.crop is not None or (FUSE_TAIL_BWD and pooled and _exact_up(*S.shape[2:]) and n7.gw is not None
+                                    and (n6.gw is not None or n6.gb is not None)):
             # nconv7's backward inside nconv6's (nconv_bwd_ex tail): its input gradient never reaches
             # HBM; its bias gradient is the sum of its output gradient (every output pixel, padding ring
             # included, as autograd's conv bias gradient), summed by the batched reduction. With the
             # cropped output nconv7's planes are the crop window from grid row / column 1
             # (step1.py:94); the gradient outside it is 0
             g9c = g9.contiguous()
-            layer_bwd(sp[7], (X[2][0], X[2][1], X[7][0], X[7][1], *W[7]), X[8][0], X[8][1], None, None,
-                      (*G[2], *G[7]), gw[7], gb[7],
-                      tail=(sp[8], *W[8], X[9][0], X[9][1], g9c, gw[8], None if ctx.crop is None else 1,
-                            *(() if gc9 is None else (gc9,))),
-                      box=wbox[2])
-            if gb[8] is not None:
-                red.add_sum(g9c, gb[8])
+            bwd(n6, y2, y5, y6, none, g2, g5, box=box6,
+                tail=TailBwd(n7.spec, n7.weight, n7.bias, n7.wsum, *y7, g9c, n7.gw,
+                             crop0=None if ctx.crop is None else 1, gcout=gc9))
+            if n7.gb is not None:
+                red.add_sum(g9c, n7.gb)
         else:
-            G[8] = (e(X[8][0]), e(X[8][1]))
-            bwd(9, 8, 0, G[8], None)                        # nconv7
-            bwd(8, 2, 7, G[2], G[7])                        # nconv6: nconv2's output (overwrite) + up
-        G[3], G[6] = (e(X[3][0]), e(X[3][1])), (e(X[6][0]), e(X[6][1]))
-        bwd(7, 3, 6, G[3], G[6], box=wbox[1])           # nconv5: down1's output + up
-        G[4], G[5] = (e(X[4][0]), e(X[4][1])), (e(X[5][0]), e(X[5][1]))
-        bwd(6, 4, 5, G[4], G[5], box=wbox[0])           # nconv4: down2's output + up
-        if ctx.pooled:
-            p2x, p2c, a2, p3x, p3c, a3, p4x, p4c, a4 = pools
-            plain = [dataclasses.replace(sp[k], mode=_lib.PLAIN) for k in (2, 3, 4)]
-            gp4 = (e(p4x), e(p4c))
-            bwd(5, 0, 0, gp4, None, src_a=(p4x, p4c), spec=plain[2])     # down3 -> pooled gradient
-            gp3 = (e(p3x), e(p3c))
-            bwd(4, 0, 0, gp3, None, src_a=(p3x, p3c), spec=plain[1], pool_grad=(*gp4, a4))  # down2
-            gp2 = (e(p2x), e(p2c))
-            bwd(3, 0, 0, gp2, None, src_a=(p2x, p2c), spec=plain[0], pool_grad=(*gp3, a3))  # down1
+            g6 = grad_of(y6)
+            bwd(n7, y6, none, y7, (g9, gc9), g6, none)
+            bwd(n6, y2, y5, y6, g6, g2, g5)             # nconv2's output (overwrite) + up
+        # -- up: nconv5 (down1's output + up), nconv4 (down2's output + up) --
+        gd1, g4 = grad_of(yd1), grad_of(y4)
+        bwd(n5, yd1, y4, y5, g5, gd1, g4, box=box5)
+        gd2, gd3 = grad_of(yd2), grad_of(yd3)
+        bwd(n4, yd2, yd3, y4, g4, gd2, gd3, box=box4)
+        # -- down: down3, down2, down1 --
+        if pooled:  # each reads its producer's pooled copy; its pooled-sized input gradient is routed
+            # into the producer's output gradient by the producer's own backward (pool_grad)
+            p2, p3, p4 = (A.p2x, A.p2c), (A.p3x, A.p3c), (A.p4x, A.p4c)
+            plain = lambda layer: dataclasses.replace(layer.spec, mode=_lib.PLAIN)  # noqa: E731
+            gp4 = grad_of(p4)
+            bwd(d3, p4, none, yd3, gd3, gp4, none, spec=plain(d3))
+            gp3 = grad_of(p3)
+            bwd(d2, p3, none, yd2, gd2, gp3, none, spec=plain(d2), pool_grad=PoolGrad(*gp4, A.a4))
+            gp2 = grad_of(p2)
+            bwd(d1, p2, none, yd1, gd1, gp2, none, spec=plain(d1), pool_grad=PoolGrad(*gp3, A.a3))
+        else:  # each pools while loading and adds into its producer's output gradient
+            bwd(d3, yd2, none, yd3, gd3, gd2, none, accumulate=True)
+            bwd(d2, yd1, none, yd2, gd2, gd1, none, accumulate=True)
+            bwd(d1, y2, none, yd1, gd1, g2, none, accumulate=True)
+        # -- head: nconv2, nconv1 --
         # nconv2's input gradient feeds nconv1's weight gradient in-tile: nconv1's backward inside nconv2's
-        head_bwd = ctx.pooled and FUSE_HEAD_BWD and not need_S
+        head_bwd = pooled and FUSE_HEAD_BWD and not need_S
+        gS = e(S) if need_S else None
         if head_bwd:
-            args = (sp[1], (X[1][0], X[1][1], None, None, *W[1]), X[2][0], X[2][1], *G[2],
-                    (None, None, None, None), gw[1], gb[1])
-            kw = dict(pool_grad=(*gp2, a2), head=(sp[0], S, *W[0], gw[0], gb[0]))
+            args = (n2.spec, n2.operands(y1, none), *y2, *g2, InputGrads(), n2.gw, n2.gb)
+            kw = dict(pool_grad=PoolGrad(*gp2, A.a2),
+                      head=HeadBwd(n1.spec, S, n1.weight, n1.bias, n1.wsum, n1.gw, n1.gb))
             if WGRAD_LAST_MAIN:  # the last layer's weight gradient after its input gradient, on this stream
                 layer_backward(*args, defer=red, **kw)
             else:
-                layer_bwd(*args, **kw)
-        elif ctx.pooled:
-            G[1] = (e(X[1][0]), e(X[1][1]))
-            bwd(2, 1, 0, G[1], None, pool_grad=(*gp2, a2))                 # nconv2
+                split(*args, **kw)
         else:
-            bwd(5, 4, 0, G[4], None, acc=True)              # down3 adds into down2's output gradient
-            bwd(4, 3, 0, G[3], None, acc=True)              # down2 -> down1's
-            bwd(3, 2, 0, G[2], None, acc=True)              # down1 -> nconv2's
-            G[1] = (e(X[1][0]), e(X[1][1]))
-            bwd(2, 1, 0, G[1], None)                        # nconv2
-        gS = e(S) if need_S else None
-        if not head_bwd:
-            layer_bwd(sp[0], (S, None, None, None, *W[0]), X[1][0], X[1][1], G[1][0], G[1][1],
-                      (gS, None, None, None), gw[0], gb[0])  # nconv1 (threshold: c0 has no gradient)
+            g1 = grad_of(y1)
+            bwd(n2, y1, none, y2, g2, g1, none, pool_grad=PoolGrad(*gp2, A.a2) if pooled else None)
+            bwd(n1, (S, None), none, y1, g1, (gS, None), none)  # (threshold: c0 has no gradient)
+        # -- the reduction --
         if side is not None:
             side.join()  # (the side stream's workspaces are handed over by WgradReduce.run)
         red.run(S.device)
-        grads = itertools.chain.from_iterable((gw[i], gb[i], None) for i in range(9))
+        grads = itertools.chain.from_iterable((layer.gw, layer.gb, None) for layer in layers)
         return (None, None, None, gS, *grads, None, None, None)  # (specs, capture, crop, S, layers, wph, w21, wbox)
 
 
@@ -506,17 +553,17 @@ class DNET(nn.Module):
         dev = S.device
         weights = [m.weight.data for m in layers]
         wsums = _wsum_views(weights, dev)
-        head = None
+        head, w21 = None, None
         l1, l2 = layers[0], layers[1]
         if nconv.FORWARD_MATH == _lib.MATH_FP32 and self._use_head(l1, l2):
-            head = (l1.weight.data, l2.weight.data,
-                    torch.empty(nconv.HEAD_WEIGHTS_FLOATS, device=dev, dtype=torch.float32))
+            w21 = torch.empty(nconv.HEAD_WEIGHTS_FLOATS, device=dev, dtype=torch.float32)
+            head = (l1.weight.data, l2.weight.data, w21)
         phase, wph = None, None
         if self._phase_layers_ok():  # (their weights are contiguous: they are among `layers`)
             wph = torch.empty((3, 1024), device=dev, dtype=torch.float32)
             phase = ([m.weight.data for m in (self.nconv4, self.nconv5, self.nconv6)], [8, 8, 0], list(wph))
         nconv.weight_prologue(weights, wsums, head=head, phase=phase)
-        return wsums, wph, (head[2] if head is not None else None)
+        return wsums, wph, w21
 
     # -- forward ----------------------------------------------------------------------------------
     def forward(self, S):

@@ -7,7 +7,7 @@ through the C ABI (include/nconv.h); there is no PyTorch or CPU fallback for it.
 """
 import os
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -335,88 +335,169 @@ class NConvLayerFn(torch.autograd.Function):
         need = ctx.needs_input_grad  # (spec, xa, ca, xb, cb, weight, bias, wsum)
         # the kernels overwrite every element of the input gradients (no zero-fill)
         z = lambda t, n: torch.empty_like(t) if (t is not None and n) else None
-        gxa, gca, gxb, gcb = z(xa, need[1]), z(ca, need[2]), z(xb, need[3]), z(cb, need[4])
+        gin = InputGrads(z(xa, need[1]), z(ca, need[2]), z(xb, need[3]), z(cb, need[4]))
         gw = torch.empty_like(weight) if need[5] else None
         gb = torch.empty_like(bias) if need[6] else None
-        layer_backward(spec, (xa, ca, xb, cb, weight, bias, wsum), y, co, gy, gco, (gxa, gca, gxb, gcb), gw, gb)
-        return None, gxa, gca, gxb, gcb, gw, gb, None, None
+        layer_backward(spec, Operands(xa, ca, xb, cb, weight, bias, wsum), y, co, gy, gco, gin, gw, gb)
+        return (None, *gin, gw, gb, None, None)
 
 
-def layer_backward(spec: LayerSpec, inputs, y, co, gy, gco, gin, gw, gb, accumulate=False, defer=None,
-                   pool_grad=None, head=None, tail=None, box=None):
-    """nconv_bwd of one fused layer: gin = (gxa, gca, gxb, gcb) (None: skip) overwritten, or added
-    into with accumulate=True (NCONV_BWD_ACCUMULATE: a tensor consumed by two layers); gw, gb
-    overwritten (None: skip). defer: a WgradReduce collecting the layer's weight-gradient partial
-    rows (NCONV_BWD_DEFER_REDUCE): gw / gb are then written by its run(). pool_grad: (gy_pool,
-    gcout_pool, argmax) -- the gradient of this layer's 2x2-pooled outputs (the next down layer read
-    layer_forward_pooled's copies), routed into gy / gco by the argmax codes (nconv_bwd_ex). head:
-    (spec, S, weight, bias, wsum, gw, gb) of the producer nconv1, whose weight / bias gradients are
-    then computed inside this layer's input gradient (nconv_bwd_ex head; gin's gxa / gca optional).
-    tail: (spec, weight, bias, wsum, y9, cout9, gy9, gw9) of the 1x1 consumer nconv7, whose backward
-    is fused into this layer's (nconv_bwd_ex tail; gy / gco are then unused and may be None; nconv7's
-    bias gradient is the caller's). The input and the weight gradient are separate kernels. tail may
-    carry a 9th element, the crop origin of nconv7's planes when they hold a window of its grid
-    (DNET's crop: nconv_bwd_io tail_crop0 / tail_h / tail_w), and a 10th, the gradient of cout9 (same
-    shape as gy9) or None: the call then goes through nconv_bwd_tail_conf. box: an exactly-2x UPCAT layer's box weights
-    (train_prologue), else built by this call."""
-    xa, ca, xb, cb, weight, bias, wsum = inputs
-    gxa, gca, gxb, gcb = gin
+class Operands(NamedTuple):
+    """What one fused layer reads (LayerSpec.descriptor's arguments): the (x, c) pairs a and b (b:
+    the second source of an UPCAT layer, else None) and the layer's weight, bias and s[o]."""
+    xa: torch.Tensor
+    ca: Optional[torch.Tensor]
+    xb: Optional[torch.Tensor]
+    cb: Optional[torch.Tensor]
+    weight: torch.Tensor
+    bias: Optional[torch.Tensor]
+    wsum: Optional[torch.Tensor]
+
+
+class InputGrads(NamedTuple):
+    """Where a layer's backward writes the gradients of Operands' xa, ca, xb, cb (None: skip)."""
+    gxa: Optional[torch.Tensor] = None
+    gca: Optional[torch.Tensor] = None
+    gxb: Optional[torch.Tensor] = None
+    gcb: Optional[torch.Tensor] = None
+
+
+class PoolGrad(NamedTuple):
+    """The gradient of a layer's 2x2-pooled outputs (the next down layer read layer_forward_pooled's
+    copies), routed into the layer's gy / gco by the pooling argmax codes."""
+    gy: torch.Tensor
+    gcout: torch.Tensor
+    argmax: torch.Tensor
+
+
+class HeadBwd(NamedTuple):
+    """The producer nconv1 of a layer reading only its output: its weight / bias gradients gw, gb
+    are computed inside that layer's input gradient (whose own gxa / gca become optional)."""
+    spec: LayerSpec
+    S: torch.Tensor
+    weight: torch.Tensor
+    bias: torch.Tensor
+    wsum: torch.Tensor
+    gw: Optional[torch.Tensor]
+    gb: Optional[torch.Tensor]
+
+
+class TailBwd(NamedTuple):
+    """The 1x1 consumer nconv7 of a layer, its backward fused into that layer's (whose gy / gco are
+    then unused and may be None): its outputs y, cout, their gradients gy and gcout (of gy's shape;
+    None: no confidence gradient) and its weight gradient gw (its bias gradient is the caller's).
+    crop0: the planes hold a window of nconv7's grid from this row / column (DNET's crop). The call
+    goes through nconv_bwd_tail_conf if gcout is given or conf_entry is set, else nconv_bwd_ex."""
+    spec: LayerSpec
+    weight: torch.Tensor
+    bias: torch.Tensor
+    wsum: torch.Tensor
+    y: torch.Tensor
+    cout: torch.Tensor
+    gy: torch.Tensor
+    gw: Optional[torch.Tensor]
+    crop0: Optional[int] = None
+    gcout: Optional[torch.Tensor] = None
+    conf_entry: bool = False
+
+
+def tail_conf_entry(tail: Optional[TailBwd]):
+    """Whether a backward with this tail is nconv_bwd_tail_conf's (else nconv_bwd_ex's)."""
+    return tail is not None and (tail.conf_entry or tail.gcout is not None)
+
+
+def bwd_io(y, co, gy, gco, gin: InputGrads, gw, gb, pool_grad=None, head=None, tail=None, box=None,
+           head_ws=(None, 0), tail_ws=(None, 0)):
+    """The nconv_bwd_io of one layer_backward call from its records, host work only. head_ws /
+    tail_ws: (address, bytes) of the head's / tail's workspace. Returns (io, head descriptor, tail
+    descriptor): io points at the descriptors (None without the record), so they live as long."""
+    io = _lib.NconvBwdIo()
+    pool = pool_grad if pool_grad is not None else PoolGrad(None, None, None)
+    for name, t in (("y", y), ("cout", co), ("gy", gy), ("gcout", gco), ("gxa", gin.gxa), ("gca", gin.gca),
+                    ("gxb", gin.gxb), ("gcb", gin.gcb), ("gw", gw), ("gbias", gb), ("gy_pool", pool.gy),
+                    ("gcout_pool", pool.gcout), ("pool_argmax", pool.argmax), ("box_weights", box)):
+        setattr(io, name, t.data_ptr() if t is not None else None)
+    HL = TL = None
+    if head is not None:
+        HL = head.spec.descriptor(head.S, None, None, None, head.weight, head.bias, head.wsum)
+        io.head = _lib.ctypes.pointer(HL)
+        io.head_workspace, io.head_workspace_bytes = head_ws
+        io.head_gw, io.head_gbias = _lib.ptr(head.gw), _lib.ptr(head.gb)
+    if tail is not None:
+        if tail.crop0 is not None:  # the planes hold a window of nconv7's grid
+            io.tail_crop0, io.tail_h, io.tail_w = int(tail.crop0), tail.y.shape[2], tail.y.shape[3]
+        TL = tail.spec.descriptor(y, co, None, None, tail.weight, tail.bias, tail.wsum)
+        io.tail = _lib.ctypes.pointer(TL)
+        io.tail_y, io.tail_cout, io.tail_gy = tail.y.data_ptr(), tail.cout.data_ptr(), tail.gy.data_ptr()
+        io.tail_workspace, io.tail_workspace_bytes = tail_ws
+        io.tail_gw = _lib.ptr(tail.gw)
+    return io, HL, TL
+
+
+def layer_backward(spec: LayerSpec, inputs: Operands, y, co, gy, gco, gin: InputGrads, gw, gb, accumulate=False,
+                   defer=None, pool_grad: Optional[PoolGrad] = None, head: Optional[HeadBwd] = None,
+                   tail: Optional[TailBwd] = None, box=None):
+    """nconv_bwd of one fused layer: gin overwritten, or added into with accumulate=True
+    (NCONV_BWD_ACCUMULATE: a tensor consumed by two layers); gw, gb overwritten (None: skip). The
+    input and the weight gradient are separate kernels. defer: a WgradReduce collecting the
+    layer's (and its head's / tail's) weight-gradient partial rows (NCONV_BWD_DEFER_REDUCE): gw / gb
+    are then written by its run(). box: an exactly-2x UPCAT layer's box weights (train_prologue),
+    else built by this call."""
     dev = y.device
     if gy is None and tail is None:
         gy = torch.zeros_like(y)
     gy = gy.contiguous() if gy is not None else None
     gco = gco.contiguous() if gco is not None else None
-    L = spec.descriptor(xa, ca, xb, cb, weight, bias, wsum)
-    lib = _lib.lib()
-    ws_bytes = lib.nconv_bwd_workspace_bytes(_lib.ctypes.byref(L))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    flags = (_lib.BWD_ACCUMULATE if accumulate else 0) | (_lib.BWD_DEFER_REDUCE if defer is not None else 0)
-    io = _lib.NconvBwdIo()
-    gpy, gpc, parg = pool_grad if pool_grad is not None else (None, None, None)
-    for name, t in (("y", y), ("cout", co), ("gy", gy), ("gcout", gco), ("gxa", gxa), ("gca", gca), ("gxb", gxb),
-                    ("gcb", gcb), ("gw", gw), ("gbias", gb), ("gy_pool", gpy), ("gcout_pool", gpc),
-                    ("pool_argmax", parg)):
-        setattr(io, name, t.data_ptr() if t is not None else None)
-    if head is not None:
-        hspec, S, hw, hb, hs, hgw, hgb = head
-        HL = hspec.descriptor(S, None, None, None, hw, hb, hs)
-        hbytes = lib.nconv_bwd_head_workspace_bytes(_lib.ctypes.byref(L))
-        hws = torch.empty(max(hbytes, 1), dtype=torch.uint8, device=dev)
-        io.head = _lib.ctypes.pointer(HL)
-        io.head_workspace, io.head_workspace_bytes = hws.data_ptr(), hbytes
-        io.head_gw, io.head_gbias = _lib.ptr(hgw), _lib.ptr(hgb)
-    io.box_weights = _lib.ptr(box)
+    L = spec.descriptor(*inputs)
+    Lp, lib = _lib.ctypes.byref(L), _lib.lib()
+
+    def workspace(nbytes_of, wanted=True):  # (tensor, (address, bytes)) of one of the call's workspaces
+        if not wanted:
+            return None, (None, 0)
+        nbytes = nbytes_of(Lp)
+        t = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        return t, (t.data_ptr(), nbytes)
+    ws, (_, ws_bytes) = workspace(lib.nconv_bwd_workspace_bytes)
+    hws, head_ws = workspace(lib.nconv_bwd_head_workspace_bytes, head is not None)
+    tws, tail_ws = workspace(lib.nconv_bwd_tail_workspace_bytes, tail is not None)
     if tail is not None:
-        tspec, tw, tb, ts, ty, tco, tgy, tgw = tail[:8]
-        if len(tail) > 8 and tail[8] is not None:  # the planes hold a window of nconv7's grid
-            io.tail_crop0, io.tail_h, io.tail_w = int(tail[8]), ty.shape[2], ty.shape[3]
-        TL = tspec.descriptor(y, co, None, None, tw, tb, ts)
-        tbytes = lib.nconv_bwd_tail_workspace_bytes(_lib.ctypes.byref(L))
-        tws = torch.empty(max(tbytes, 1), dtype=torch.uint8, device=dev)
-        io.tail = _lib.ctypes.pointer(TL)
-        io.tail_y, io.tail_cout, io.tail_gy = ty.data_ptr(), tco.data_ptr(), tgy.contiguous().data_ptr()
-        io.tail_workspace, io.tail_workspace_bytes = tws.data_ptr(), tbytes
-        io.tail_gw = _lib.ptr(tgw)
-    if tail is not None and len(tail) > 9:
-        tgco = tail[9]
-        if tgco is not None:
-            if tgco.shape != tgy.shape:
-                raise ValueError(f"layer_backward: tail gcout {tuple(tgco.shape)} does not match gy "
-                                 f"{tuple(tgy.shape)}")
-            tgco = tgco.contiguous()
-        rc = lib.nconv_bwd_tail_conf(_lib.ctypes.byref(L), _lib.ctypes.byref(io), _lib.ptr(tgco), _lib.ptr(ws),
-                                     ws_bytes, flags, _lib.stream_handle(dev))
+        if tail.gcout is not None and tail.gcout.shape != tail.gy.shape:
+            raise ValueError(f"layer_backward: tail gcout {tuple(tail.gcout.shape)} does not match gy "
+                             f"{tuple(tail.gy.shape)}")
+        tail = tail._replace(gy=tail.gy.contiguous(), gcout=None if tail.gcout is None else tail.gcout.contiguous())
+    io, HL, TL = bwd_io(y, co, gy, gco, gin, gw, gb, pool_grad, head, tail, box, head_ws, tail_ws)
+    flags = (_lib.BWD_ACCUMULATE if accumulate else 0) | (_lib.BWD_DEFER_REDUCE if defer is not None else 0)
+    rest = (_lib.ptr(ws), ws_bytes, flags, _lib.stream_handle(dev))
+    if tail_conf_entry(tail):
+        rc = lib.nconv_bwd_tail_conf(Lp, _lib.ctypes.byref(io), _lib.ptr(tail.gcout), *rest)
     else:
-        rc = lib.nconv_bwd_ex(_lib.ctypes.byref(L), _lib.ctypes.byref(io), _lib.ptr(ws), ws_bytes, flags,
-                              _lib.stream_handle(dev))
+        rc = lib.nconv_bwd_ex(Lp, _lib.ctypes.byref(io), *rest)
     if defer is not None and rc >= 0:
         defer.add(L, ws, rc, gw, gb)
         if head is not None:
-            defer.add(HL, hws, io.head_nparts, hgw, hgb)
+            defer.add(HL, hws, io.head_nparts, head.gw, head.gb)
         if tail is not None:
-            defer.add(TL, tws, io.tail_nparts, tgw, None)
+            defer.add(TL, tws, io.tail_nparts, tail.gw, None)
         return
     _lib.check(rc, "nconv_bwd")
+
+
+class WgradJob(NamedTuple):
+    """One layer's deferred reduction: its descriptor, the workspace holding its nparts partial
+    rows, the gradients to write and the stream the workspace was allocated on."""
+    layer: object
+    ws: torch.Tensor
+    nparts: int
+    gw: Optional[torch.Tensor]
+    gb: Optional[torch.Tensor]
+    stream: object
+
+
+class SumJob(NamedTuple):
+    """out[0] = x.sum(); stream: the one x was made on."""
+    x: torch.Tensor
+    out: torch.Tensor
+    stream: object
 
 
 class WgradReduce:
@@ -430,41 +511,36 @@ class WgradReduce:
 
     def add(self, L, ws, nparts, gw, gb):
         if nparts > 0 and (gw is not None or gb is not None):  # (input-gradient-only calls add none)
-            self.jobs.append((L, ws, nparts, gw, gb, torch.cuda.current_stream(ws.device)))
+            self.jobs.append(WgradJob(L, ws, nparts, gw, gb, torch.cuda.current_stream(ws.device)))
 
     def add_sum(self, x, out):
         """out[0] = x.sum() in the same two launches (nconv_wgrad_reduce_ex; fixed order)."""
-        self.sums.append((x.contiguous(), out, torch.cuda.current_stream(x.device)))
+        self.sums.append(SumJob(x.contiguous(), out, torch.cuda.current_stream(x.device)))
 
     def run(self, device):
         cur = torch.cuda.current_stream(device)
-        for j in self.jobs:
-            # a workspace allocated on another stream (the weight-gradient side stream) is read here
-            # by the current one: keep the allocator from reusing it before this reduction ran
-            if j[5] != cur:
-                j[1].record_stream(cur)
-        for j in self.sums:
-            if j[2] != cur:
-                j[0].record_stream(cur)
-        items = [("job", j) for j in self.jobs] + [("sum", j) for j in self.sums]
-        lib = _lib.lib()
+        # a workspace allocated on another stream (the weight-gradient side stream) is read here
+        # by the current one: keep the allocator from reusing it before this reduction ran
+        for t, stream in [(j.ws, j.stream) for j in self.jobs] + [(s.x, s.stream) for s in self.sums]:
+            if stream != cur:
+                t.record_stream(cur)
+        items = self.jobs + self.sums
+        lib, P, I = _lib.lib(), _lib.ctypes.c_void_p, _lib.ctypes.c_int
         for k in range(0, len(items), 16):
-            jobs = [j for t, j in items[k:k + 16] if t == "job"]
-            sums = [j for t, j in items[k:k + 16] if t == "sum"]
+            jobs = [j for j in items[k:k + 16] if isinstance(j, WgradJob)]
+            sums = [j for j in items[k:k + 16] if isinstance(j, SumJob)]
             n, ns = len(jobs), len(sums)
-            VP = _lib.ctypes.c_void_p * max(n, 1)
-            layers = (_lib.NconvLayer * max(n, 1))(*[j[0] for j in jobs])
-            wss = VP(*[j[1].data_ptr() for j in jobs])
-            nparts = (_lib.ctypes.c_int * max(n, 1))(*[j[2] for j in jobs])
-            gws = VP(*[(j[3].data_ptr() if j[3] is not None else None) for j in jobs])
-            gbs = VP(*[(j[4].data_ptr() if j[4] is not None else None) for j in jobs])
-            SP = _lib.ctypes.c_void_p * max(ns, 1)
+            VP, SP = P * max(n, 1), P * max(ns, 1)
             sws_bytes = lib.nconv_sum_workspace_bytes(ns)
             sws = torch.empty(max(sws_bytes, 4), dtype=torch.uint8, device=device) if ns else None
-            rc = lib.nconv_wgrad_reduce_ex(n, layers, wss, nparts, gws, gbs, ns, SP(*[j[0].data_ptr() for j in sums]),
-                                           (_lib.ctypes.c_longlong * max(ns, 1))(*[j[0].numel() for j in sums]),
-                                           SP(*[j[1].data_ptr() for j in sums]), _lib.ptr(sws), sws_bytes,
-                                           _lib.stream_handle(device))
+            rc = lib.nconv_wgrad_reduce_ex(
+                n, (_lib.NconvLayer * max(n, 1))(*[j.layer for j in jobs]), VP(*[j.ws.data_ptr() for j in jobs]),
+                (I * max(n, 1))(*[j.nparts for j in jobs]),
+                VP(*[(j.gw.data_ptr() if j.gw is not None else None) for j in jobs]),
+                VP(*[(j.gb.data_ptr() if j.gb is not None else None) for j in jobs]),
+                ns, SP(*[s.x.data_ptr() for s in sums]),
+                (_lib.ctypes.c_longlong * max(ns, 1))(*[s.x.numel() for s in sums]),
+                SP(*[s.out.data_ptr() for s in sums]), _lib.ptr(sws), sws_bytes, _lib.stream_handle(device))
             _lib.check(rc, "nconv_wgrad_reduce")
         self.jobs = []
         self.sums = []

@@ -69,3 +69,24 @@ def test_dnet_args_round_trip(D, absent):
     back = D.DNETArgs.unflatten(flat)
     assert all(a is b for x, y in zip(back.layers, layers) for a, b in zip(x, y)) and len(back.layers) == 9
     assert back.wph is wph and back.w21 is w21 and back.wbox is wbox
+
+
+ACT_ORDER = ("x1 c1 x2 c2 x3 c3 x4 c4 x5 c5 x6 c6 x7 c7 x8 c8 x9 c9 "
+             "p2x p2c a2 p3x p3c a3 p4x p4c a4").split()
+
+
+@pytest.mark.parametrize("pooled", [True, False])
+def test_train_acts_round_trip(D, pooled):
+    """DNETFn's saved activations: the flat order handed to save_for_backward is the record's field order, 27
+    tensors with the pooled graph's copies and argmax codes and the first 18 without; the backward rebuilds the
+    record from that flat form."""
+    assert list(D.TrainActs._fields) == ACT_ORDER
+    n = 27 if pooled else 18
+    named = {name: torch.full((1,), float(k)) for k, name in enumerate(ACT_ORDER[:n])}
+    acts = D.TrainActs(**named)
+    flat = acts.flatten()
+    assert len(flat) == n and all(t is named[name] for t, name in zip(flat, ACT_ORDER))
+    back = D.TrainActs(*flat)
+    assert back == acts and all(getattr(back, name) is named.get(name) for name in ACT_ORDER)
+    assert all(x is named[f"x{k}"] and c is named[f"c{k}"] for k, (x, c) in enumerate(back.outputs(), 1))
+    assert len(back.outputs()) == 9

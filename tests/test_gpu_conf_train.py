@@ -168,17 +168,17 @@ def _tail_case(nconv_amd, gpu, H, W, window):
                 gc9=gc9)
 
 
-def _tail_fused(nconv_amd, gpu, k, window, gc9, ten=True):
+def _tail_fused(nconv_amd, gpu, k, window, gc9, conf_entry=True):
     N = nconv_amd.nconv
     e = torch.empty_like
-    gin = (e(k["x2"]), e(k["c2"]), e(k["x7"]), e(k["c7"]))
+    gin = N.InputGrads(e(k["x2"]), e(k["c2"]), e(k["x7"]), e(k["c7"]))
     gw6, gb6, gw7 = e(k["W6"][0]), e(k["W6"][1]), e(k["W7"][0])
     cut = (lambda t: t) if window is None else (lambda t: t[:, :, 1:1 + window[0], 1:1 + window[1]].contiguous())
-    tail = (k["sp7"], *k["W7"], cut(k["x9"]), cut(k["c9"]), cut(k["g9"]), gw7, None if window is None else 1)
-    if ten:
-        tail += (None if gc9 is None else cut(gc9),)
-    N.layer_backward(k["sp6"], (k["x2"], k["c2"], k["x7"], k["c7"], *k["W6"]), k["x8"], k["c8"], None, None, gin,
-                     gw6, gb6, tail=tail)
+    tail = N.TailBwd(k["sp7"], *k["W7"], cut(k["x9"]), cut(k["c9"]), cut(k["g9"]), gw7,
+                     crop0=None if window is None else 1, gcout=None if gc9 is None else cut(gc9),
+                     conf_entry=conf_entry)
+    N.layer_backward(k["sp6"], N.Operands(k["x2"], k["c2"], k["x7"], k["c7"], *k["W6"]), k["x8"], k["c8"], None, None,
+                     gin, gw6, gb6, tail=tail)
     torch.cuda.synchronize()
     return (*gin, gw6, gb6, gw7)
 
@@ -196,18 +196,19 @@ def test_tail_conf_matches_two_general_backwards(nconv_amd, gpu, H, W, window):
     e = torch.empty_like
     g8 = (e(k["x8"]), e(k["c8"]))
     gw7 = e(k["W7"][0])
-    N.layer_backward(k["sp7"], (k["x8"], k["c8"], None, None, *k["W7"]), k["x9"], k["c9"], k["g9"], k["gc9"],
-                     (*g8, None, None), gw7, None)
-    gin = (e(k["x2"]), e(k["c2"]), e(k["x7"]), e(k["c7"]))
+    N.layer_backward(k["sp7"], N.Operands(k["x8"], k["c8"], None, None, *k["W7"]), k["x9"], k["c9"], k["g9"],
+                     k["gc9"], N.InputGrads(*g8), gw7, None)
+    gin = N.InputGrads(e(k["x2"]), e(k["c2"]), e(k["x7"]), e(k["c7"]))
     gw6, gb6 = e(k["W6"][0]), e(k["W6"][1])
-    N.layer_backward(k["sp6"], (k["x2"], k["c2"], k["x7"], k["c7"], *k["W6"]), k["x8"], k["c8"], *g8, gin, gw6, gb6)
+    N.layer_backward(k["sp6"], N.Operands(k["x2"], k["c2"], k["x7"], k["c7"], *k["W6"]), k["x8"], k["c8"], *g8, gin,
+                     gw6, gb6)
     torch.cuda.synchronize()
     for name, a, b in zip(("gxa", "gca", "gxb", "gcb", "gw6", "gb6", "gw7"), got, (*gin, gw6, gb6, gw7)):
         rel = ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
         print(f"{name}: {rel:.2e}")
         assert torch.isfinite(a).all() and rel <= 1e-5, f"{name}: {rel:.2e}"
     null = _tail_fused(nconv_amd, gpu, k, window, None)           # nconv_bwd_tail_conf(tail_gcout = NULL)
-    ex = _tail_fused(nconv_amd, gpu, k, window, None, ten=False)  # nconv_bwd_ex
+    ex = _tail_fused(nconv_amd, gpu, k, window, None, conf_entry=False)  # nconv_bwd_ex
     assert all(torch.equal(a, b) for a, b in zip(null, ex))
     assert not torch.equal(null[1], got[1])  # and the plane changes the result
 
