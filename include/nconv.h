@@ -1436,6 +1436,107 @@ int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long
                          long long tgt_channel_stride, long long tgt_row_stride, const float* gloss,
                          const void* workspace, size_t workspace_bytes, float* g_depth, void* stream);
 
+/* Edge-aware depth smoothness loss and its edge weights (new entry points only: no existing struct or
+ * signature changes, so NCONV_ABI_VERSION stays 27). The regulariser the photometric term above is trained
+ * with: on road, sky and walls every depth explains the image equally well, so the papers pair the term with
+ * a penalty on the predicted depth's differences -- the L1 of its first differences, relaxed where the image
+ * itself has an edge (monodepth: Godard, Mac Aodha, Brostow, CVPR 2017; order = 1), or the L1 of its second
+ * differences (Ma, Cavalheiro, Karaman, ICRA 2019; order = 2). Every pixel of the gradient gathers its own
+ * stencil: no atomics, the same bits on every run.
+ *
+ * The rule, fp32, one rounding per operation in the order written, no contraction. Per image b: d the depth
+ * view (B, H, W); M(i, j) = 0 <= i < H && 0 <= j < W && (mask == NULL || mask[b][i][j] != 0); the optional
+ * weights w (B, 2, H, W) contiguous, wx(i, j) = w[b][0][i][j] the weight of the edge between columns j and
+ * j + 1 (column W - 1 is never read), wy(i, j) = w[b][1][i][j] that of the edge between rows i and i + 1 (row
+ * H - 1 is never read); weights == NULL: every weight is 1 and no multiply is made. min(a, b) = b < a ? b : a.
+ *   order 1     x, 0 <= j <= W - 2:  cx = M(i, j) && M(i, j + 1)       tx = d[i][j + 1] - d[i][j]    ox = wx(i, j)
+ *               y, 0 <= i <= H - 2:  cy = M(i, j) && M(i + 1, j)       ty = d[i + 1][j] - d[i][j]    oy = wy(i, j)
+ *   order 2     x, 1 <= j <= W - 2:  cx = M(i, j - 1) && M(i, j) && M(i, j + 1)
+ *                                    tx = (d[i][j - 1] + d[i][j + 1]) - (2.0f * d[i][j])
+ *                                    ox = min(wx(i, j - 1), wx(i, j))
+ *               y, 1 <= i <= H - 2:  likewise down the column with wy
+ *   both        sx = cx ? ox * |tx| : 0                sy likewise
+ *               n_x, n_y = the numbers of true cx, cy, integers counted on the device
+ *               L  = (float)(Sx / (double)max(n_x, 1) + Sy / (double)max(n_y, 1)),  Sx = sum sx, Sy = sum sy
+ *               kx = gloss * (1.0f / (float)max(n_x, 1))      ky likewise        (gloss NULL: 1)
+ *               qx(i, j) = cx ? (kx * ox) * sign(tx) : +0.0f  qy likewise        (sign(t) = t > 0 ? 1 : t < 0 ? -1 : 0)
+ *   order 1     g_depth(i, j) = ((qx(i, j - 1) - qx(i, j)) + qy(i - 1, j)) - qy(i, j)
+ *   order 2     g_depth(i, j) = (((qx(i, j - 1) + qx(i, j + 1)) - (2.0f * qx(i, j)))
+ *                                + (qy(i - 1, j) + qy(i + 1, j))) - (2.0f * qy(i, j))
+ *               a q outside its range is +0.0f.
+ * Sx and Sy are summed separately: fp32 partials over the photometric loss's fixed 16 x 64 tiles (a term
+ * belongs to the pixel (i, j) it is written at), in its lane and wave order; tiles and images combined in
+ * double in a fixed order; L formed in double and rounded to fp32 once. A NaN depth makes the terms it
+ * touches NaN (and their q 0); a masked-out depth is never multiplied in. A 1-wide or 1-high image has
+ * n_x or n_y equal to 0. nconv_smooth_loss_fwd leaves L in loss[0] and n_x, n_y in the first two ints of the
+ * workspace; nconv_smooth_loss_bwd reads them there: no host synchronisation.
+ *
+ * The edge weights of a frame I (B, C, H, W), C = 1 or 3, alpha >= 0:
+ *               e[ch] = |I[b][ch][i][j + 1] - I[b][ch][i][j]|
+ *               g     = C == 1 ? e[0] : ((e[0] + e[1]) + e[2]) / 3.0f
+ *               wx(i, j) = E(alpha * g);   wy(i, j) likewise from I[b][ch][i + 1][j]
+ *               wx(i, W - 1) = wy(H - 1, j) = 1.0f  (written, never read by the loss)
+ * E(x) stands for exp(-x), x >= 0, and is these operations (no library or hardware exponential: their
+ * bits differ between hosts and the device):
+ *               y = x * 1.44269504f;   y = y < 126.0f ? y : 126.0f      (a NaN or huge x ends at 126)
+ *               n = rintf(y)            (to nearest, ties to even)       r = n - y   (exact, |r| <= 0.5)
+ *               p = c6;  p = p * r + c5;  ..  p = p * r + c0             (Horner, product and sum rounded apiece)
+ *               c0 .. c6 = 1.0f, 0.693147182f, 0.240226507f, 0.0555041097f, 0.00961812865f,
+ *                          0.00133335579f, 0.000154035297f               (ln(2)^k / k!)
+ *               E = n > 125.0f ? +0.0f : p * 2^-n                        (the bits (127 - (int)n) << 23: exact)
+ * so weights below 2^-125.5 (x above 86.9), and those of a NaN, are +0. How far E departs from float64
+ * exp(-x) is a measurement (tests/smooth_cases.py e_error: every g an 8-bit frame produces and 4097
+ * significands of every binade of alpha g, g in [0, 255], where E is not flushed), largest relative error:
+ *               E_MAX_REL_ERR   alpha = 1/255: 2.343e-07   alpha = 1: 3.805e-06 ;
+ * the second is the rounding of x * log2(e) at y near 125.
+ *
+ * NOT offered: normalising the depth by its mean (or a disparity); the mixed derivative d_xy; a gradient
+ * with respect to the weights or the image (both are inputs).
+ * (the entry points are nconv_smooth_loss_fwd / _bwd; the descriptor's type is `struct nconv_smooth_loss`
+ * or nconv_smooth_loss_desc) */
+typedef struct nconv_smooth_loss {
+    int B, H, W;                    /* depth, mask, g_depth: B planes of H rows of W               */
+    int order;                      /* 1: first differences (monodepth); 2: second (Ma et al.)     */
+    const float* depth;             /* fp32 view, 4-byte aligned                                   */
+    long long depth_image_stride;   /* elements; ignored when B == 1                               */
+    long long depth_row_stride;     /* elements, >= W                                              */
+    const unsigned char* mask;      /* uint8 view (B, H, W), or NULL: every pixel takes part       */
+    long long mask_image_stride;    /* bytes; ignored when B == 1                                  */
+    long long mask_row_stride;      /* bytes, >= W                                                 */
+    const float* weights;           /* fp32 (B, 2, H, W) contiguous (nconv_edge_weights), or NULL  */
+} nconv_smooth_loss_desc;
+
+/* workspace: nconv_smooth_loss_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or
+ * B * H * W >= 2^31); the forward writes it, the backward reads its first two ints (n_x, n_y). loss, gloss:
+ * device scalars (gloss NULL: 1). g_depth: (B, H, W) fp32 contiguous, OVERWRITTEN, not overlapping depth.
+ * Two launches forward, one backward; no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch: a NULL descriptor or depth; order outside {1, 2}; B, H or W <= 0;
+ * B * H * W >= 2^31; a pointer that is not aligned to its element; a view whose strides are negative or
+ * smaller than its rows / images, or one plane of which spans 2^31 bytes or more ("plane too large"); a NULL
+ * loss or g_depth; g_depth overlapping depth; a workspace that is NULL, too small or not 8-byte aligned. */
+size_t nconv_smooth_loss_workspace_bytes(int B, int H, int W);
+int nconv_smooth_loss_fwd(const struct nconv_smooth_loss* d, float* loss, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int nconv_smooth_loss_bwd(const struct nconv_smooth_loss* d, const float* gloss, const void* workspace,
+                          size_t workspace_bytes, float* g_depth, void* stream);
+
+/* (the entry point is nconv_edge_weights; the descriptor's type is `struct nconv_edge_weights` or
+ * nconv_edge_weights_desc) */
+typedef struct nconv_edge_weights {
+    int B, C, H, W;                 /* C = 1 or 3 channels                                         */
+    const float* image;             /* fp32 view: B images of C planes of H rows of W              */
+    long long image_stride;         /* elements; ignored when B == 1                               */
+    long long channel_stride;       /* elements; ignored when C == 1                               */
+    long long row_stride;           /* elements, >= W                                              */
+    float alpha;                    /* >= 0, finite; the monodepth recipe on 8-bit values: 1 / 255 */
+} nconv_edge_weights_desc;
+
+/* weights: (B, 2, H, W) fp32 contiguous, OVERWRITTEN, not overlapping the image. One launch on `stream`.
+ * -EINVAL before any launch: a NULL descriptor, image or weights; C outside {1, 3}; B, H or W <= 0;
+ * B * C * H * W >= 2^31; alpha negative, NaN or infinite; a misaligned pointer; a view refused as above;
+ * weights overlapping the image. */
+int nconv_edge_weights(const struct nconv_edge_weights* d, float* weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,10 @@ EXPORTED = (
     "nconv_photo_loss_workspace_bytes",
     "nconv_photo_loss_fwd",
     "nconv_photo_loss_bwd",
+    "nconv_smooth_loss_workspace_bytes",
+    "nconv_smooth_loss_fwd",
+    "nconv_smooth_loss_bwd",
+    "nconv_edge_weights",
 )
 
 
@@ -198,6 +202,20 @@ class NconvLidarProject(ctypes.Structure):
                 ("points", ctypes.c_void_p), ("n_rows", ctypes.c_longlong), ("offsets", ctypes.c_void_p),
                 ("m", ctypes.c_void_p), ("m_image_stride", ctypes.c_longlong), ("z_min", ctypes.c_float),
                 ("z_max", ctypes.c_float)]
+
+
+class NconvSmoothLoss(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("order", ctypes.c_int),
+                ("depth", ctypes.c_void_p), ("depth_image_stride", ctypes.c_longlong),
+                ("depth_row_stride", ctypes.c_longlong), ("mask", ctypes.c_void_p),
+                ("mask_image_stride", ctypes.c_longlong), ("mask_row_stride", ctypes.c_longlong),
+                ("weights", ctypes.c_void_p)]
+
+
+class NconvEdgeWeights(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("image", ctypes.c_void_p), ("image_stride", ctypes.c_longlong),
+                ("channel_stride", ctypes.c_longlong), ("row_stride", ctypes.c_longlong), ("alpha", ctypes.c_float)]
 
 
 class NconvDepthColorize(ctypes.Structure):
@@ -434,6 +452,14 @@ def _declare(lib):
     lib.nconv_photo_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P]
     lib.nconv_photo_loss_bwd.restype = I
     lib.nconv_photo_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P, P]
+    lib.nconv_smooth_loss_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_smooth_loss_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_smooth_loss_fwd.restype = I
+    lib.nconv_smooth_loss_fwd.argtypes = [ctypes.POINTER(NconvSmoothLoss), P, P, ctypes.c_size_t, P]
+    lib.nconv_smooth_loss_bwd.restype = I
+    lib.nconv_smooth_loss_bwd.argtypes = [ctypes.POINTER(NconvSmoothLoss), P, P, ctypes.c_size_t, P, P]
+    lib.nconv_edge_weights.restype = I
+    lib.nconv_edge_weights.argtypes = [ctypes.POINTER(NconvEdgeWeights), P, P]
 
 
 def lib():

@@ -1,7 +1,7 @@
 // capi_io.hip — the extern "C" entry points of the device-side I/O families: loss, metrics, frame ingest
 // and export, back-projection, normals, LiDAR projection, colourise, sparsify, occlusion, augment,
-// sparsification curves, the IP-Basic baseline, the nearest-sample transform, and the view warp with its
-// photometric loss.
+// sparsification curves, the IP-Basic baseline, the nearest-sample transform, the view warp with its
+// photometric loss, and the depth smoothness loss with its edge weights.
 // Host code only: each validates its descriptor, fills the family's argument struct (nconv_internal.h)
 // and calls its launcher (capi_common.h).
 #include "capi_common.h"
@@ -833,6 +833,88 @@ int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long
     if (!g_depth) return fail(-22, fn, "null g_depth");
     if ((size_t)gloss % 4 || (size_t)g_depth % 4) return fail(-22, fn, "gloss / g_depth not 4-byte aligned");
     return launched(fn, nconv::launch_photo_loss_bwd, a, gloss, workspace, g_depth, (hipStream_t)stream);
+}
+
+size_t nconv_smooth_loss_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::smooth_loss_workspace_bytes(B, H, W);
+}
+
+// The descriptor of nconv_smooth_loss_* and the workspace checked and turned into the kernels' arguments.
+static const char* smooth_args(const nconv_smooth_loss* d, const void* ws, size_t ws_bytes, nconv::SmoothArgs& a,
+                               std::string& text) {
+    if (!d) return "null descriptor";
+    if (!d->depth) return "null depth";
+    if (d->order != 1 && d->order != 2) return "order must be 1 or 2";
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return "non-positive B/H/W";
+    const int B = d->B, H = d->H, W = d->W;
+    if ((long long)B * H * W >= (1LL << 31)) return "batch too large: B * H * W must be below 2^31";
+    if ((size_t)d->depth % 4 || (size_t)d->weights % 4) return "depth / weights not 4-byte aligned";
+    a = nconv::SmoothArgs{};
+    a.B = B, a.H = H, a.W = W, a.order = d->order, a.w = d->weights;
+    if (const char* why = view_args(d->depth, B, H, W, 4, d->depth_image_stride, d->depth_row_stride, kNoStrideLimit, 16,
+                                    kViewPoints, a.depth)) {
+        text = std::string("depth: ") + why;
+        return text.c_str();
+    }
+    if (d->mask) {
+        if (const char* why = view_args(d->mask, B, H, W, 1, d->mask_image_stride, d->mask_row_stride, kNoStrideLimit,
+                                        4, kViewPoints, a.mask)) {
+            text = std::string("mask: ") + why;
+            return text.c_str();
+        }
+    }
+    if (!ws || ws_bytes < nconv::smooth_loss_workspace_bytes(B, H, W)) return "workspace too small";
+    if ((size_t)ws % 8) return "workspace not 8-byte aligned";
+    return nullptr;
+}
+
+int nconv_smooth_loss_fwd(const struct nconv_smooth_loss* d, float* loss, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    const char* fn = "nconv_smooth_loss_fwd";
+    nconv::SmoothArgs a;
+    std::string text;
+    if (const char* why = smooth_args(d, workspace, workspace_bytes, a, text)) return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    if ((size_t)loss % 4) return fail(-22, fn, "loss not 4-byte aligned");
+    return launched(fn, nconv::launch_smooth_loss_fwd, a, loss, workspace, (hipStream_t)stream);
+}
+
+int nconv_smooth_loss_bwd(const struct nconv_smooth_loss* d, const float* gloss, const void* workspace,
+                          size_t workspace_bytes, float* g_depth, void* stream) {
+    const char* fn = "nconv_smooth_loss_bwd";
+    nconv::SmoothArgs a;
+    std::string text;
+    if (const char* why = smooth_args(d, workspace, workspace_bytes, a, text)) return fail(-22, fn, why);
+    if (!g_depth) return fail(-22, fn, "null g_depth");
+    if ((size_t)gloss % 4 || (size_t)g_depth % 4) return fail(-22, fn, "gloss / g_depth not 4-byte aligned");
+    // every pixel of g_depth is written while its neighbours' depths are still being read
+    const Extent eg = flat_extent(g_depth, (long long)a.B * a.H * a.W * 4, "g_depth");
+    if (eg.overlaps(view_extent(d->depth, a.B, a.H, a.W, a.depth.bs, 0, a.depth.rs, 1, 4, "depth")))
+        return fail(-22, fn, "g_depth overlaps depth");
+    return launched(fn, nconv::launch_smooth_loss_bwd, a, gloss, workspace, g_depth, (hipStream_t)stream);
+}
+
+int nconv_edge_weights(const struct nconv_edge_weights* d, float* weights, void* stream) {
+    const char* fn = "nconv_edge_weights";
+    if (!d) return fail(-22, fn, "null descriptor");
+    if (!d->image || !weights) return fail(-22, fn, "null image or weights");
+    if (d->C != 1 && d->C != 3) return fail(-22, fn, "C must be 1 or 3");
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(-22, fn, "non-positive B/H/W");
+    if ((long long)d->B * d->C * d->H * d->W >= (1LL << 31))
+        return fail(-22, fn, "batch too large: B * C * H * W must be below 2^31");
+    if (!(d->alpha >= 0.f) || d->alpha > __FLT_MAX__) return fail(-22, fn, "alpha must be finite and >= 0");
+    if ((size_t)d->image % 4 || (size_t)weights % 4) return fail(-22, fn, "image / weights not 4-byte aligned");
+    nconv::EdgeArgs a{};
+    std::string text;
+    a.B = d->B, a.C = d->C, a.H = d->H, a.W = d->W, a.alpha = d->alpha;
+    if (const char* why = warp_image_view("image", d->image, a.B, a.C, a.H, a.W, d->image_stride, d->channel_stride,
+                                          d->row_stride, a.img, a.cs, text))
+        return fail(-22, fn, why);
+    const Extent ew = flat_extent(weights, (long long)a.B * 2 * a.H * a.W * 4, "weights");
+    if (ew.overlaps(view_extent(d->image, a.B, a.H, a.W, a.img.bs, a.cs, a.img.rs, a.C, 4, "image")))
+        return fail(-22, fn, "weights overlaps image");
+    return launched(fn, nconv::launch_edge_weights, a, weights, (hipStream_t)stream);
 }
 
 }  // extern "C"

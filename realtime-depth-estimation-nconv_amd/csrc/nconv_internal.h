@@ -486,4 +486,23 @@ int launch_photo_loss_fwd(const WarpArgs& a, float* loss, void* ws, hipStream_t 
 int launch_photo_loss_bwd(const WarpArgs& a, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
                           const char** why);
 
+// Edge-aware depth smoothness loss and the edge weights (nconv_smooth_loss_*, nconv_edge_weights), smooth_loss.hip.
+struct SmoothArgs {
+    int B, H, W, order;       // order 1: first differences, 2: second differences
+    PlaneView depth;          // fp32 (B, H, W), strides in elements (wide is not used: one pixel per lane)
+    PlaneView mask;           // base null: none; uint8 (B, H, W), strides in bytes
+    const float* w;           // null: every weight 1; fp32 (B, 2, H, W) contiguous, wx then wy
+};
+size_t smooth_loss_workspace_bytes(int B, int H, int W);
+int launch_smooth_loss_fwd(const SmoothArgs& a, float* loss, void* ws, hipStream_t st, const char** why);
+int launch_smooth_loss_bwd(const SmoothArgs& a, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
+                           const char** why);
+struct EdgeArgs {
+    int B, C, H, W;           // C = 1 or 3
+    PlaneView img;            // fp32 (B, C, H, W); rs / bs of one channel plane, channels cs apart
+    long long cs;
+    float alpha;
+};
+int launch_edge_weights(const EdgeArgs& a, float* w, hipStream_t st, const char** why);
+
 }  // namespace nconv

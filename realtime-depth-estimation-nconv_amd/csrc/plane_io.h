@@ -1,7 +1,7 @@
 // plane_io.h — reading a strided view of 2-D planes on the device, and the grid of pixel tiles the
 // kernels over such planes are launched on, defined once. Every kernel that takes a PlaneView reads it
 // through these loaders (the loss, confidence-loss and metrics kernels, frame_io, backproject, normals,
-// colorize, occlusion, ipbasic, nearest, augment, view_warp); the NConv staging (nconv_common.h) and
+// colorize, occlusion, ipbasic, nearest, augment, view_warp, smooth_loss); the NConv staging (nconv_common.h) and
 // lidar_project.hip take the resource constants and ld_f32.
 //
 // A view is a batch of planes given as (base, image stride, row stride): PlaneView below, checked and
@@ -122,7 +122,7 @@ __device__ __forceinline__ TileOrigin tile_origin(int H, int W) {
     return o;
 }
 
-// The 16 x 64 tile of the loss family (loss.hip, conf_loss.hip, metrics.hip, view_warp.hip): 1024
+// The 16 x 64 tile of the loss family (loss.hip, conf_loss.hip, metrics.hip, view_warp.hip, smooth_loss.hip): 1024
 // pixels, four per thread of a 256-thread workgroup.
 constexpr int kLossTH = 16, kLossTW = 64;
 __host__ __device__ __forceinline__ int loss_tiles_per_image(int H, int W) {

@@ -10,7 +10,7 @@
 //                   waves_in_order. block_sum4_again is the same with a barrier before the write, for
 //                   a caller that passes the same red to consecutive calls.
 //   image_tile_sums the finalize stage of the per-tile partial sums (conf_loss.hip, metrics.hip,
-//                   view_warp.hip): by one wave, lane l adds its image's tiles l, l + 64, .. in that
+//                   view_warp.hip, smooth_loss.hip): by one wave, lane l adds its image's tiles l, l + 64, .. in that
 //                   order in double, then wave_sum. The caller adds the images in order.
 //   wave_incl_scan  the inclusive prefix over the lanes of a wave by __shfl_up 1, 2, .., 32.
 //   block_excl_scan the exclusive prefix over the threads of NWAVES waves in thread order, and the

@@ -14,6 +14,8 @@ to the current frame, and let the gradient flow into the depth.
                       reaches memory)
   PhotometricLoss     the same as an nn.Module
   ViewWarper          the same with outputs and workspace kept between calls (hipGraph capture)
+  halve_intrinsics    k of a half-resolution pyramid level made by 2 x 2 average pooling
+  halve_projection    m of that level
 
 The rule (include/nconv.h, fp32, one rounding per operation): P = pointcloud.backproject's point of the
 pixel at depth z; (a, b, c) = m . (P, 1) with lidar.project_points' dot; u = a / c, v = b / c; the pixel is
@@ -23,7 +25,8 @@ coordinates, F.grid_sample's align_corners=True), an invalid one is 0 and has no
 are the same bits on every run: each target pixel owns its four taps, so the depth's gradient is a gather.
 
 Not offered: a gradient with respect to the source image (a scatter) or to m (poses are inputs), SSIM,
-an image pyramid (downsample the frames and scale k and m yourself), pose estimation. Device tensors
+a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
+halve_projection(m): dividing k by 2 is wrong by half a pixel), pose estimation. Device tensors
 only: there is no PyTorch path.
 """
 import ctypes
@@ -54,6 +57,32 @@ def warp_projection(k_src, pose):
     last = rt.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(rt.shape[:-2] + (1, 4))
     m = p @ torch.cat((rt, last), dim=-2)                      # [K | 0] . [R t; 0 1] = [K R | K t]
     return (m if m.dim() == 3 else m[None]).float().contiguous()
+
+
+def _halved(x, what, shape):
+    _views.require_tensor(x, what, (torch.float32, torch.float64), PREFIX)
+    if x.dim() not in (2, 3) or tuple(x.shape[-2:]) != shape:
+        raise ValueError(f"{PREFIX}: {what} must be {shape} or a batch of them, got {tuple(x.shape)}")
+    return x.double().clone()
+
+
+def halve_intrinsics(k):
+    """The intrinsics of a half-resolution level made by 2 x 2 average pooling, whose pixel j' sits at the
+    full-resolution coordinate 2 j' + 0.5 (pixel centres at integer coordinates, as view_warp fixes them):
+    fx' = fx / 2, cx' = (cx - 0.5) / 2, likewise in y; plain k / 2 is wrong by half a pixel. k: (3, 3) or
+    (B, 3, 3), float32 or float64; computed in float64 and rounded once to k's dtype."""
+    h = _halved(k, "k", (3, 3))
+    h[..., :2, :] = (h[..., :2, :] - 0.5 * h[..., 2:3, :]) / 2
+    return h.to(k.dtype)
+
+
+def halve_projection(m):
+    """The projection K_src . [R | t] into the half-resolution level of the source frame (halve_intrinsics of
+    K_src applied to m): rows 0 and 1 become (row - 0.5 row 2) / 2. m: (3, 4) or (B, 3, 4); computed in
+    float64 and rounded once to m's dtype."""
+    h = _halved(m, "m", (3, 4))
+    h[..., :2, :] = (h[..., :2, :] - 0.5 * h[..., 2:3, :]) / 2
+    return h.to(m.dtype)
 
 
 def _image_view(x, what, B, C):
