@@ -1385,8 +1385,8 @@ int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long lo
  * nconv_photo_loss_bwd reads n_v from the same workspace: no host synchronisation.
  *
  * NOT offered: a gradient with respect to the source image (a scatter); a gradient with respect to m
- * (poses are inputs); SSIM; an image pyramid (a caller downsamples and scales k and m themselves); pose
- * estimation. An invalid pixel loads no tap, a valid one reads taps inside the source plane by the
+ * (poses are inputs); an image pyramid (a caller downsamples and scales k and m themselves); pose
+ * estimation. (The SSIM term is nconv_photo_ssim_loss_* below.) An invalid pixel loads no tap, a valid one reads taps inside the source plane by the
  * clamps: no byte outside a view's extent is read.
  * (the entry points are nconv_view_warp_fwd / _bwd; the descriptor's type is `struct nconv_view_warp`
  * or nconv_view_warp_desc) */
@@ -1435,6 +1435,82 @@ int nconv_photo_loss_fwd(const struct nconv_view_warp* d, const float* tgt, long
 int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
                          long long tgt_channel_stride, long long tgt_row_stride, const float* gloss,
                          const void* workspace, size_t workspace_bytes, float* g_depth, void* stream);
+
+/* The photometric loss with its structural term (new entry points only: no existing struct or signature
+ * changes, so NCONV_ABI_VERSION stays 27): L = alpha Lw + (1 - alpha) Lv, the loss monodepth, monodepth2 and Ma
+ * et al.'s follow-ups train with (alpha = 0.85), Lv the L1 term above and Lw the mean of (1 - SSIM) / 2 over
+ * 3 x 3 windows of the warped and the target frame. The descriptor, valid(p), s[ch] and the taps are exactly
+ * nconv_view_warp's. The derivative of a window's SSIM with respect to a warped pixel q of it is affine in
+ * (x_q, y_q), so a pixel's gradient is a sum of three coefficients over the up to nine windows that hold it
+ * and the depth's gradient stays a gather: no atomics, the same bits on every run.
+ *
+ * The rule, fp32, one rounding per operation in the order written, no contraction. Per channel ch,
+ * x = s[ch] (the warped value of a valid pixel) and y = tgt[b][ch].
+ *   window     a pixel p = (b, i, j) has a window iff 1 <= i <= H - 2, 1 <= j <= W - 2 and all nine pixels of its
+ *              3 x 3 neighbourhood are valid; a pixel outside the image counts as not valid. This DIFFERS from
+ *              monodepth's ReflectionPad2d(1) on purpose, by a one-pixel frame: "a term counts where all its
+ *              pixels count", the smoothness loss's convention, which keeps the backward a plain box sum.
+ *              n_w = the number of pixels with a window, n_v = the number of valid pixels, integers counted on
+ *              the device.
+ *   sums       over the window's nine pixels in raster order (row i - 1 first, columns j - 1, j, j + 1),
+ *              sequential, the first element taken as it is:
+ *              Sx = sum x    Sy = sum y    Sxx = sum (x * x)    Syy = sum (y * y)    Sxy = sum (x * y)
+ *   moments    mux = Sx / 9.0f                    muy = Sy / 9.0f
+ *              vx  = (Sxx / 9.0f) - (mux * mux)   vy  = (Syy / 9.0f) - (muy * muy)
+ *              vxy = (Sxy / 9.0f) - (mux * muy)                                  (monodepth's formulation)
+ *   SSIM       A1 = (2.0f * (mux * muy)) + c1               A2 = (2.0f * vxy) + c2
+ *              B1 = ((mux * mux) + (muy * muy)) + c1        B2 = (vx + vy) + c2
+ *              D  = B1 * B2         ssim = (A1 * A2) / D                        (IEEE division)
+ *              t  = (1.0f - ssim) * 0.5f
+ *              e[ch] = t < 0 ? 0 : t > 1 ? 1 : t            (a NaN stays NaN)
+ *              pass  = t >= 0 && t <= 1                     (where torch.clamp passes the gradient)
+ *              x == y gives ssim == 1.0f exactly (the products by 2 are exact, so A1 == B1 and A2 == B2).
+ *   constants  c1 = (0.01 R)^2, c2 = (0.03 R)^2 for the data range R (255 for 8-bit-valued frames, 1 for
+ *              [0, 1]), formed in double by the caller, rounded once to fp32 and passed as floats.
+ *   loss       termw = window ? (C == 1 ? e[0] : (e[0] + e[1]) + e[2]) : 0
+ *              Lw = (float)(sum termw / ((double)C * (double)max(n_w, 1)))
+ *              Lv = nconv_photo_loss_fwd's L: the same terms, the same fp32 tile partials, the same tree
+ *              L  = (alpha * Lw) + ((1.0f - alpha) * Lv)
+ *              The SSIM terms are a second fp32 partial over the same 16 x 64 tiles (a term belongs to the
+ *              window's centre), in the same lane and wave order; tiles and images combined in double in the
+ *              same fixed order, as the smoothness loss's two sums are.
+ *   backward   d ssim_p / d x_q = a_p + b_p x_q + c_p y_q for a pixel q of the window p, with
+ *              c_p = (2.0f * A1) / (9.0f * D)
+ *              b_p = -((2.0f * ssim) / (9.0f * B2))
+ *              sm  = ssim * mux
+ *              a_p = (2.0f * ((((muy * (A2 - A1)) / D) - (sm / B1)) + (sm / B2))) / 9.0f
+ *              SA(q), SB(q), SC(q) = the sums of a, b, c over the nine window positions centred at
+ *              (i - 1 .. i + 1, j - 1 .. j + 1) in raster order, sequential from +0.0f; a position that is
+ *              no window or does not pass contributes +0.0f
+ *              den_v = (float)C * (float)max(n_v, 1)         den_w = (float)C * (float)max(n_w, 1)
+ *              kl = (gloss * (1.0f - alpha)) * (1.0f / den_v)             (gloss NULL: 1)
+ *              kq = (alpha * 0.5f) * (gloss * (1.0f / den_w))
+ *              g_x(q)  = -(kq * ((SA + (SB * x_q)) + (SC * y_q)))
+ *              g_s[ch] = (kl * sign(x_q - y_q)) + g_x(q)
+ *              and g_depth from g_s as nconv_view_warp's derivatives state.
+ * REQUIRED PROPERTY: at alpha = 0 (and finite sums), L and g_depth equal nconv_photo_loss_*'s on the same
+ * operands (g_x is a zero, kl is kk). nconv_photo_ssim_loss_fwd leaves L in loss[0] and n_v, n_w in the first
+ * two ints of the workspace; the backward reads them there: no host synchronisation, and it recomputes the
+ * warp of the tile and its halo from the depth: the forward saves no planes, and nothing per-pixel except
+ * g_depth reaches memory.
+ *
+ * NOT offered: reflection padding; windows other than 3 x 3 (no Gaussian window); a per-pixel error map;
+ * the minimum reprojection over several sources; auto-masking; a gradient to the images. Whether the SSIM
+ * term improves the error on KITTI with this network has not been measured by anyone.
+ *
+ * workspace: nconv_photo_ssim_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or B * H * W
+ * >= 2^31). tgt, loss, gloss and g_depth as nconv_photo_loss_*'s. Two launches forward, one backward; no
+ * atomics, no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch: everything nconv_photo_loss_* refuses; alpha outside [0, 1] or NaN; c1 or c2
+ * not finite or not > 0; a workspace that is NULL, too small or not 8-byte aligned. */
+size_t nconv_photo_ssim_workspace_bytes(int B, int H, int W);
+int nconv_photo_ssim_loss_fwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                              long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
+                              float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                              long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
+                              const float* gloss, const void* workspace, size_t workspace_bytes, float* g_depth,
+                              void* stream);
 
 /* Edge-aware depth smoothness loss and its edge weights (new entry points only: no existing struct or
  * signature changes, so NCONV_ABI_VERSION stays 27). The regulariser the photometric term above is trained

@@ -113,6 +113,9 @@ EXPORTED = (
     "nconv_photo_loss_workspace_bytes",
     "nconv_photo_loss_fwd",
     "nconv_photo_loss_bwd",
+    "nconv_photo_ssim_workspace_bytes",
+    "nconv_photo_ssim_loss_fwd",
+    "nconv_photo_ssim_loss_bwd",
     "nconv_smooth_loss_workspace_bytes",
     "nconv_smooth_loss_fwd",
     "nconv_smooth_loss_bwd",
@@ -452,6 +455,13 @@ def _declare(lib):
     lib.nconv_photo_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P]
     lib.nconv_photo_loss_bwd.restype = I
     lib.nconv_photo_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, P, P, ctypes.c_size_t, P, P]
+    lib.nconv_photo_ssim_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_photo_ssim_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_photo_ssim_loss_fwd.restype = I
+    lib.nconv_photo_ssim_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, F, F, F, P, P, ctypes.c_size_t, P]
+    lib.nconv_photo_ssim_loss_bwd.restype = I
+    lib.nconv_photo_ssim_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, F, F, F, P, P, ctypes.c_size_t,
+                                              P, P]
     lib.nconv_smooth_loss_workspace_bytes.restype = ctypes.c_size_t
     lib.nconv_smooth_loss_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_smooth_loss_fwd.restype = I

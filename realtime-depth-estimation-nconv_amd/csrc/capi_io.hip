@@ -835,6 +835,57 @@ int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long
     return launched(fn, nconv::launch_photo_loss_bwd, a, gloss, workspace, g_depth, (hipStream_t)stream);
 }
 
+size_t nconv_photo_ssim_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::photo_ssim_workspace_bytes(B, H, W);
+}
+
+// The SSIM loss's own operands, after warp_args: the target frame, the mixing weight, the constants and
+// the workspace.
+static const char* ssim_args(const nconv_view_warp* d, const float* tgt, long long tbs, long long tcs, long long trs,
+                             float alpha, float c1, float c2, const void* ws, size_t ws_bytes, nconv::WarpArgs& a,
+                             std::string& text) {
+    if (const char* why = warp_args(d, a, text)) return why;
+    if (!tgt) return "null tgt";
+    if ((size_t)tgt % 4) return "tgt not 4-byte aligned";
+    if (const char* why = warp_image_view("tgt", tgt, a.B, a.C, a.H, a.W, tbs, tcs, trs, a.tgt, a.tcs, text)) return why;
+    if (!(alpha >= 0.f && alpha <= 1.f)) return "alpha must be in [0, 1] (and not NaN)";
+    if (!(c1 > 0.f && c1 <= __FLT_MAX__) || !(c2 > 0.f && c2 <= __FLT_MAX__)) return "c1 and c2 must be finite and > 0";
+    if (!ws || ws_bytes < nconv::photo_ssim_workspace_bytes(a.B, a.H, a.W)) return "workspace too small";
+    if ((size_t)ws % 8) return "workspace not 8-byte aligned";
+    return nullptr;
+}
+
+int nconv_photo_ssim_loss_fwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                              long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
+                              float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_photo_ssim_loss_fwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = ssim_args(d, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, alpha, c1, c2,
+                                    workspace, workspace_bytes, a, text))
+        return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    if ((size_t)loss % 4) return fail(-22, fn, "loss not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_ssim_loss_fwd, a, alpha, c1, c2, loss, workspace, (hipStream_t)stream);
+}
+
+int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long long tgt_image_stride,
+                              long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
+                              const float* gloss, const void* workspace, size_t workspace_bytes, float* g_depth,
+                              void* stream) {
+    const char* fn = "nconv_photo_ssim_loss_bwd";
+    nconv::WarpArgs a;
+    std::string text;
+    if (const char* why = ssim_args(d, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, alpha, c1, c2,
+                                    workspace, workspace_bytes, a, text))
+        return fail(-22, fn, why);
+    if (!g_depth) return fail(-22, fn, "null g_depth");
+    if ((size_t)gloss % 4 || (size_t)g_depth % 4) return fail(-22, fn, "gloss / g_depth not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_ssim_loss_bwd, a, alpha, c1, c2, gloss, workspace, g_depth,
+                    (hipStream_t)stream);
+}
+
 size_t nconv_smooth_loss_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
     return nconv::smooth_loss_workspace_bytes(B, H, W);

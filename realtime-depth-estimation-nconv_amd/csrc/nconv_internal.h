@@ -485,6 +485,12 @@ int launch_view_warp_bwd(const WarpArgs& a, const float* g_warped, float* g_dept
 int launch_photo_loss_fwd(const WarpArgs& a, float* loss, void* ws, hipStream_t st, const char** why);
 int launch_photo_loss_bwd(const WarpArgs& a, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
                           const char** why);
+// The same loss with the SSIM term over 3 x 3 windows (nconv_photo_ssim_loss_*), photo_ssim.hip.
+size_t photo_ssim_workspace_bytes(int B, int H, int W);
+int launch_photo_ssim_loss_fwd(const WarpArgs& a, float alpha, float c1, float c2, float* loss, void* ws,
+                               hipStream_t st, const char** why);
+int launch_photo_ssim_loss_bwd(const WarpArgs& a, float alpha, float c1, float c2, const float* gloss, const void* ws,
+                               float* g_depth, hipStream_t st, const char** why);
 
 // Edge-aware depth smoothness loss and the edge weights (nconv_smooth_loss_*, nconv_edge_weights), smooth_loss.hip.
 struct SmoothArgs {

@@ -12,7 +12,10 @@ to the current frame, and let the gradient flow into the depth.
   photometric_loss    mean over valid pixels and channels of |warped - tgt| with the warp fused in
                       (nconv_photo_loss_fwd / _bwd: two launches forward, one backward; warped never
                       reaches memory)
-  PhotometricLoss     the same as an nn.Module
+  photometric_ssim_loss  alpha / 2 (1 - SSIM) + (1 - alpha) L1, the loss the monodepth family trains with, over
+                      3 x 3 windows of all-valid pixels, the warp fused in (nconv_photo_ssim_loss_fwd / _bwd:
+                      two launches forward, one backward; neither warped nor any SSIM plane reaches memory)
+  PhotometricLoss     either loss as an nn.Module (alpha = 0: the L1 path)
   ViewWarper          the same with outputs and workspace kept between calls (hipGraph capture)
   halve_intrinsics    k of a half-resolution pyramid level made by 2 x 2 average pooling
   halve_projection    m of that level
@@ -24,8 +27,15 @@ pixel is the bilinear blend of the four source pixels around (v, u) (pixel centr
 coordinates, F.grid_sample's align_corners=True), an invalid one is 0 and has no gradient. The results
 are the same bits on every run: each target pixel owns its four taps, so the depth's gradient is a gather.
 
-Not offered: a gradient with respect to the source image (a scatter) or to m (poses are inputs), SSIM,
-a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
+The SSIM term (include/nconv.h, nconv_photo_ssim_loss_*): a pixel has a window iff it is not on the image's
+one-pixel frame and all nine pixels of its 3 x 3 neighbourhood are valid -- not monodepth's
+ReflectionPad2d(1), on purpose: a term counts where all its pixels count, as in smooth.py; the means, variances
+and the covariance are monodepth's E[xy] - E[x] E[y] over the window, c1 = (0.01 R)^2, c2 = (0.03 R)^2 for the
+data range R, and the term is clamp((1 - SSIM) / 2, 0, 1) averaged over windows and channels.
+
+Not offered: a gradient with respect to the source image (a scatter) or to m (poses are inputs); for the SSIM
+term reflection padding, windows other than 3 x 3, a per-pixel error map, the minimum reprojection over
+several sources and auto-masking; a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
 halve_projection(m): dividing k by 2 is wrong by half a pixel), pose estimation. Device tensors
 only: there is no PyTorch path.
 """
@@ -269,19 +279,106 @@ def photometric_loss(depth, k, tgt, src, m, mask=None, z_min=0.0, z_max=None, re
     return (loss, n_v) if return_valid_count else loss
 
 
+def _ssim_constants(alpha, data_range):
+    """(alpha, c1, c2) as Python floats: c1 = (0.01 R)^2 and c2 = (0.03 R)^2 formed in double (ctypes rounds
+    them to fp32 once). alpha and data_range are Python numbers, not tensors: constants of a captured graph."""
+    if torch.is_tensor(alpha) or torch.is_tensor(data_range):
+        raise TypeError(f"{PREFIX}: alpha and data_range must be Python floats (they are constants of the call, "
+                        "and of a captured graph), not tensors")
+    alpha, R = float(alpha), float(data_range)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{PREFIX}: alpha = {alpha} is outside [0, 1]")
+    c1, c2 = (0.01 * R) ** 2, (0.03 * R) ** 2
+    f32 = torch.finfo(torch.float32)
+    if not (R > 0.0 and f32.tiny <= c1 and c2 <= f32.max):
+        raise ValueError(f"{PREFIX}: data_range = {R} must be positive and finite, with (0.01 R)^2 and (0.03 R)^2 "
+                         "normal fp32 numbers")
+    return alpha, c1, c2
+
+
+def ssim_workspace_bytes(B, H, W):
+    """Bytes of photometric_ssim_loss's workspace (nconv_photo_ssim_workspace_bytes); its first two int32 are
+    n_v and n_w."""
+    from . import _lib
+    B, H, W = int(B), int(H), int(W)
+    if B <= 0 or H <= 0 or W <= 0 or B * H * W >= 2 ** 31:
+        raise ValueError(f"{PREFIX}: a batch of (B, H, W) = {(B, H, W)} is empty or too large (B * H * W < 2^31)")
+    return _lib.lib().nconv_photo_ssim_workspace_bytes(B, H, W)
+
+
+class PhotoSsimLossFn(torch.autograd.Function):
+    """photometric_ssim_loss's kernels (nconv_photo_ssim_loss_fwd / _bwd); the gradient reaches the depth alone."""
+
+    @staticmethod
+    def forward(ctx, depth, k, tgt, src, m, mask, consts, z_min, z_max, out):
+        from . import _lib
+        d, (B, C, H, W), t, mask = _descriptor(depth, k, src, m, mask, z_min, z_max, tgt)
+        dev = depth.device
+        nbytes = ssim_workspace_bytes(B, H, W)
+        ws = _views.output(out, "workspace", (nbytes,), torch.uint8, dev, PREFIX, source="depth")
+        loss = _views.output(out, "loss", (), torch.float32, dev, PREFIX, source="depth")
+        rc = _lib.lib().nconv_photo_ssim_loss_fwd(ctypes.byref(d), _lib.ptr(tgt), t[0], t[1], t[2], *consts,
+                                                  _lib.ptr(loss), _lib.ptr(ws), nbytes, _lib.stream_handle(dev))
+        _lib.check(rc, "nconv_photo_ssim_loss_fwd")
+        ctx.z, ctx.consts = (z_min, z_max), consts
+        ctx.g_depth = None if out is None else out.get("g_depth")
+        ctx.save_for_backward(depth, k, tgt, src, m, mask, ws)
+        n = ws[:8].view(torch.int32)
+        n_v, n_w = n[0], n[1]
+        ctx.mark_non_differentiable(n_v, n_w)
+        return loss, n_v, n_w
+
+    @staticmethod
+    def backward(ctx, gloss, _g_nv, _g_nw):
+        from . import _lib
+        depth, k, tgt, src, m, mask, ws = ctx.saved_tensors
+        d, (B, C, H, W), t, _ = _descriptor(depth, k, src, m, mask, *ctx.z, tgt)
+        gloss = gloss.contiguous()
+        g = ctx.g_depth if ctx.g_depth is not None else torch.empty((B, 1, H, W), dtype=torch.float32,
+                                                                    device=depth.device)
+        rc = _lib.lib().nconv_photo_ssim_loss_bwd(ctypes.byref(d), _lib.ptr(tgt), t[0], t[1], t[2], *ctx.consts,
+                                                  _lib.ptr(gloss), _lib.ptr(ws), ws.numel(), _lib.ptr(g),
+                                                  _lib.stream_handle(depth.device))
+        _lib.check(rc, "nconv_photo_ssim_loss_bwd")
+        return g, None, None, None, None, None, None, None, None, None
+
+
+def photometric_ssim_loss(depth, k, tgt, src, m, mask=None, alpha=0.85, data_range=255.0, z_min=0.0, z_max=None,
+                          return_counts=False, out=None):
+    """alpha Lw + (1 - alpha) Lv: Lv is photometric_loss's L1 mean over the n_v valid pixels, Lw the mean over
+    the n_w windows and the channels of clamp((1 - SSIM) / 2, 0, 1), SSIM over the 3 x 3 window of a pixel whose
+    nine pixels are all valid (no reflection padding: the image's one-pixel frame has no window). A scalar on the
+    device, or (loss, n_v, n_w) with return_counts, the counts int32 views of the workspace (no host
+    synchronisation). alpha (monodepth: 0.85) and data_range (255 for 8-bit-valued frames, 1 for [0, 1]; c1 =
+    (0.01 R)^2, c2 = (0.03 R)^2) are Python floats, captured as constants by a graph. The operands as
+    photometric_loss's; differentiable in depth only: a src, tgt, k or m that requires a gradient is refused.
+    out: an optional dict of kept contiguous buffers 'workspace' (uint8, ssim_workspace_bytes(B, H, W)), 'loss',
+    'g_depth' (B, 1, H, W). Two launches forward, one backward; the backward recomputes the warp of each tile and
+    its halo, so neither warped nor any SSIM plane reaches memory. At alpha = 0 the loss and the gradient equal
+    photometric_loss's."""
+    consts = _ssim_constants(alpha, data_range)
+    loss, n_v, n_w = PhotoSsimLossFn.apply(depth, k, tgt, src, m, mask, consts, z_min, z_max, out)
+    return (loss, n_v, n_w) if return_counts else loss
+
+
 class PhotometricLoss(torch.nn.Module):
     """photometric_loss with its depth window held: loss(depth, k, tgt, src, m, mask=None). In a
     training step: calculate_loss(pred, gt, True) + w * photo(pred, k, rgb, rgb_near, m), with m refilled
-    in place per batch (a GraphedTrainStep input)."""
+    in place per batch (a GraphedTrainStep input). alpha = 0 (the default) is the L1 loss, exactly as before;
+    alpha > 0 is photometric_ssim_loss with that alpha and data_range (Python floats, constants of a capture)."""
 
-    def __init__(self, z_min=0.0, z_max=None):
+    def __init__(self, z_min=0.0, z_max=None, alpha=0.0, data_range=255.0):
         super().__init__()
         if not float(z_min) >= 0.0 or (z_max is not None and not float(z_max) >= float(z_min)):
             raise ValueError(f"{PREFIX}: need 0 <= z_min <= z_max, got z_min={z_min}, z_max={z_max}")
         self.z_min, self.z_max = float(z_min), None if z_max is None else float(z_max)
+        self.alpha, _, _ = _ssim_constants(alpha, data_range)
+        self.data_range = float(data_range)
 
     def forward(self, depth, k, tgt, src, m, mask=None):
-        return photometric_loss(depth, k, tgt, src, m, mask, self.z_min, self.z_max)
+        if self.alpha == 0.0:
+            return photometric_loss(depth, k, tgt, src, m, mask, self.z_min, self.z_max)
+        return photometric_ssim_loss(depth, k, tgt, src, m, mask, self.alpha, self.data_range, self.z_min, self.z_max)
 
 
 class ViewWarper:
@@ -289,15 +386,20 @@ class ViewWarper:
     between calls: no allocation after construction, so the calls can be captured with torch.cuda.graph
     and replayed on operands refilled in place. warper(depth, k, src, m) -> warped (or (warped, valid));
     warper.loss(depth, k, tgt, src, m) -> loss (or (loss, n_v)). The returned tensors are the kept ones,
-    overwritten by the next call; the warp and the loss keep separate gradient buffers."""
+    overwritten by the next call; the warp and the loss keep separate gradient buffers. alpha > 0: .loss is
+    photometric_ssim_loss with that alpha and data_range (Python floats) and its own kept workspace, loss
+    and gradient buffer; alpha = 0 (the default) is the L1 loss as before."""
 
-    def __init__(self, size, src_size=None, B=1, C=3, device=None, z_min=0.0, z_max=None):
+    def __init__(self, size, src_size=None, B=1, C=3, device=None, z_min=0.0, z_max=None, alpha=0.0,
+                 data_range=255.0):
         H, W = (int(v) for v in size)
         Hs, Ws = (H, W) if src_size is None else (int(v) for v in src_size)
         if min(H, W, Hs, Ws, int(B)) <= 0 or int(C) not in (1, 3):
             raise ValueError(f"{PREFIX}: sizes must be positive and C 1 or 3, got {size}, {src_size}, B={B}, C={C}")
         self.size, self.src_size, self.B, self.C = (H, W), (Hs, Ws), int(B), int(C)
         self.z_min, self.z_max = z_min, z_max
+        self.alpha, _, _ = _ssim_constants(alpha, data_range)
+        self.data_range = float(data_range)
         dev = torch.device("cuda" if device is None else device)
         f32 = dict(dtype=torch.float32, device=dev)
         self._warp = {"warped": torch.empty(self.B, self.C, H, W, **f32),
@@ -305,6 +407,10 @@ class ViewWarper:
                       "g_depth": torch.empty(self.B, 1, H, W, **f32)}
         self._loss = {"workspace": torch.empty(workspace_bytes(self.B, H, W), dtype=torch.uint8, device=dev),
                       "loss": torch.empty((), **f32), "g_depth": torch.empty(self.B, 1, H, W, **f32)}
+        self._ssim = None
+        if self.alpha != 0.0:
+            self._ssim = {"workspace": torch.empty(ssim_workspace_bytes(self.B, H, W), dtype=torch.uint8, device=dev),
+                          "loss": torch.empty((), **f32), "g_depth": torch.empty(self.B, 1, H, W, **f32)}
 
     def _check(self, depth, src):
         if torch.is_tensor(depth) and torch.is_tensor(src) and depth.dim() == 4 and src.dim() == 4:
@@ -319,5 +425,9 @@ class ViewWarper:
 
     def loss(self, depth, k, tgt, src, m, mask=None, return_valid_count=False):
         self._check(depth, src)
+        if self._ssim is not None:
+            r = photometric_ssim_loss(depth, k, tgt, src, m, mask, self.alpha, self.data_range, self.z_min,
+                                      self.z_max, return_valid_count, out=self._ssim)
+            return r[:2] if return_valid_count else r
         return photometric_loss(depth, k, tgt, src, m, mask, self.z_min, self.z_max, return_valid_count,
                                 out=self._loss)
