@@ -1385,8 +1385,8 @@ int nconv_depth_nearest(const struct nconv_depth_nearest* d, float* dst, long lo
  * nconv_photo_loss_bwd reads n_v from the same workspace: no host synchronisation.
  *
  * NOT offered: a gradient with respect to the source image (a scatter); a gradient with respect to m
- * (poses are inputs); an image pyramid (a caller downsamples and scales k and m themselves); pose
- * estimation. (The SSIM term is nconv_photo_ssim_loss_* below.) An invalid pixel loads no tap, a valid one reads taps inside the source plane by the
+ * (poses are inputs); an image pyramid (a caller downsamples and scales k and m themselves). (The SSIM term is
+ * nconv_photo_ssim_loss_* below; the pose itself comes from nconv_pose_normal_eq / nconv_pose_update.) An invalid pixel loads no tap, a valid one reads taps inside the source plane by the
  * clamps: no byte outside a view's extent is read.
  * (the entry points are nconv_view_warp_fwd / _bwd; the descriptor's type is `struct nconv_view_warp`
  * or nconv_view_warp_desc) */
@@ -1511,6 +1511,112 @@ int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt,
                               long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
                               const float* gloss, const void* workspace, size_t workspace_bytes, float* g_depth,
                               void* stream);
+
+/* Relative camera pose from sparse depth by direct image alignment (new entry points only: no existing struct
+ * or signature changes, so NCONV_ABI_VERSION stays 27). The m = K_src . [R | t] that nconv_view_warp_*,
+ * nconv_photo_loss_* and nconv_photo_ssim_loss_* take as an input, estimated from what a training batch holds:
+ * the sparse depth of the current (target) frame gives 3-D points, and the pose is the one that minimises the
+ * intensity difference between the target frame at those pixels and the neighbouring (source) frame at their
+ * projections (Kerl, Sturm, Cremers, ICRA 2013; LSD-SLAM's tracker), by damped Gauss-Newton on SE(3). One
+ * iteration is nconv_pose_normal_eq followed by nconv_pose_update.
+ *
+ * nconv_pose_normal_eq, fp32, one rounding per operation in the order written, no contraction. Per target
+ * pixel (b, i, j): P = (x, y, z), u, v, valid, the taps, s[ch], dIu[ch] and dIv[ch] are nconv_view_warp's with
+ * the current m, bit for bit (a pixel is a sample iff it is valid there: z > z_min && z <= z_max, its mask, its
+ * projection inside the source). With p the current fp32 pose [R | t] of image b (row-major 3 x 4) and
+ * fxs = K_src[0][0], fys = K_src[1][1]:
+ *     point      X' = dot(p[0], P)   Y' = dot(p[1], P)   Z' = dot(p[2], P)        (nconv_lidar_project's dot)
+ *                xn = X' / Z'   yn = Y' / Z'   iz = 1.0f / Z'   xx = xn * xn   yy = yn * yn   xy = xn * yn
+ *     Ju         [fxs * iz, 0, -(fxs * (xn * iz)), -(fxs * xy), fxs * (1.0f + xx), -(fxs * yn)]
+ *     Jv         [0, fys * iz, -(fys * (yn * iz)), -(fys * (1.0f + yy)), fys * xy, fys * xn]
+ *     J[ch]      J[0] = dIu * Ju[0]   J[1] = dIv * Jv[1]   J[k] = (dIu * Ju[k]) + (dIv * Jv[k]), k = 2 .. 5
+ *                the derivative of s[ch] for a left perturbation xi = (nu, omega), dP' = nu + omega x P'
+ *     residual   r = s[ch] - tgt[b][ch][i][j]      ar = |r|
+ *     weight     w = (huber == 0 || ar <= huber) ? 1.0f : huber / ar                (Huber; 0: least squares)
+ *     terms      wj[k] = w * J[k]   h[k][l] = wj[k] * J[l] (k <= l, row-major upper triangle: 21)
+ *                bk[k] = wj[k] * r (6)   e = (w * r) * r
+ *                each of the 28 summed over the channels as (t[0] + t[1]) + t[2] (C == 1: t[0]); 0 where the
+ *                pixel is not valid
+ * The sums are the photometric loss's: fp32 partials over fixed 16 x 64 tiles in nconv_photo_loss_fwd's lane and
+ * wave order, the exact count n of valid pixels per tile; no atomics.
+ *
+ * nconv_pose_update, one wave per image, all of it in double (IEEE, the order written, no contraction):
+ *     sums       S[0 .. 27], n: the image's tiles combined in double in nconv_photo_loss_fwd's fixed order
+ *     history    cost[b][it] = (float)(S[27] / ((double)C * (double)max(n, 1)))       n_hist[b][it] = n
+ *     apply == 0 stops here (the cost at the pose already reached). Otherwise:
+ *     system     A = H (symmetric, from S[0 .. 20]), A[k][k] = A[k][k] + ((double)damping * A[k][k]), g = -S[21 + k]
+ *     solve      A = L D L^T, the square-root-free Cholesky (only + - x /, so that a host restatement gives the
+ *                same bits), for j = 0 .. 5: v[k] = L[j][k] * D[k] and d = A[j][j] - sum_{k < j} L[j][k] * v[k]
+ *                (k ascending, each product subtracted in turn); D[j] = d; L[i][j] = (A[i][j] - sum_{k < j}
+ *                L[i][k] * v[k]) / d for i > j. Then y[i] = g[i] - sum_{k < i} L[i][k] * y[k] and, for
+ *                i = 5 .. 0, delta[i] = y[i] / D[i] - sum_{k > i} L[k][i] * delta[k] (k ascending).
+ *     status     1: n < min_points; 2: a pivot d that is not finite or <= 0; 3: a delta that is not finite;
+ *                0 otherwise. A nonzero status leaves the pose as it is (delta = 0).
+ *     retraction (Cayley: only + - x /, unlike sin / cos) a = delta[3 .. 5] / 2, qkl = a[k] * a[l],
+ *                f = 2 / (1 + ((q00 + q11) + q22)), dR = I + f ([a]x + [a]x^2):
+ *                dR[0][0] = 1 + f * (-(q11 + q22))   dR[0][1] = f * (-a2 + q01)   dR[0][2] = f * (a1 + q02)
+ *                dR[1][0] = f * (a2 + q01)   dR[1][1] = 1 + f * (-(q00 + q22))   dR[1][2] = f * (-a0 + q12)
+ *                dR[2][0] = f * (-a1 + q02)  dR[2][1] = f * (a0 + q12)    dR[2][2] = 1 + f * (-(q00 + q11))
+ *                [R | t] <- dR . [R | t] with (dR[i][0] * P[0][j] + dR[i][1] * P[1][j]) + dR[i][2] * P[2][j],
+ *                then t[i] <- t[i] + delta[i]
+ *     outputs    pose[b] = (float)[R | t];  m[b][i][j] = (float)((Ks[i][0] * P[0][j] + Ks[i][1] * P[1][j]) +
+ *                Ks[i][2] * P[2][j]) with Ks = (double)K_src, for the next nconv_pose_normal_eq
+ * The pose state is the double (B, 3, 4) at the start of the workspace, so that orthogonality does not drift with
+ * the fp32 rounding of `pose`; THE CALLER INITIALISES IT (and pose and m to match) before the first iteration.
+ * The B x 28 doubles after it are the sums S as the last update combined them.
+ *
+ * NOT offered: feature matching or PnP; RANSAC; a step-acceptance test (true Levenberg-Marquardt: the damping is
+ * fixed); joint refinement of the depth; more than one source per call; affine brightness correction; an image
+ * pyramid (a caller runs the levels, coarse to fine, on its own downsampled operands).
+ *
+ * The descriptor is nconv_view_warp's fields, then the new ones. m and pose are read by nconv_pose_normal_eq and
+ * rewritten by nconv_pose_update; with B > 1 each image has its own m (m_image_stride >= 12). status: (B) int;
+ * cost, n_hist: (B, history) fp32 / int rows, entry `it` written by nconv_pose_update(.., it, ..). workspace:
+ * nconv_pose_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or B * H * W >= 2^31). One launch
+ * each; no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch: everything nconv_photo_loss_fwd refuses of the shared fields and tgt; a NULL k_src,
+ * pose, status, cost or n_hist; a pointer that is not 4-byte aligned; a negative k_src image stride; with B > 1
+ * an m_image_stride below 12; a negative or NaN huber or damping; min_points < 6; history <= 0; it outside
+ * [0, history); a workspace that is NULL, too small or not 8-byte aligned. */
+typedef struct nconv_pose_align {
+    int B, C;                       /* C = 1 or 3 channels of src and tgt                          */
+    int H, W;                       /* the target view: depth, mask, tgt                           */
+    int Hs, Ws;                     /* the source frame                                            */
+    const float* depth;             /* the sparse depth of the target: fp32 view, B planes of H x W */
+    long long depth_image_stride;   /* elements; ignored when B == 1                               */
+    long long depth_row_stride;     /* elements, >= W                                              */
+    const unsigned char* mask;      /* uint8 view (B, H, W), or NULL                               */
+    long long mask_image_stride;    /* bytes; ignored when B == 1                                  */
+    long long mask_row_stride;      /* bytes, >= W                                                 */
+    const float* src;               /* fp32 view: B images of C planes of Hs rows of Ws            */
+    long long src_image_stride;     /* elements; ignored when B == 1                               */
+    long long src_channel_stride;   /* elements; ignored when C == 1                               */
+    long long src_row_stride;       /* elements, >= Ws                                             */
+    const float* k;                 /* device: 3 x 3 row-major intrinsics of the target camera     */
+    long long k_image_stride;       /* floats between the matrices of two images; 0: one camera    */
+    float* m;                       /* device: 3 x 4 row-major K_src . [R | t], read and REWRITTEN */
+    long long m_image_stride;       /* floats between the matrices of two images, >= 12 (B > 1)    */
+    float z_min, z_max;             /* a sample: z > z_min && z <= z_max; z_max == 0: FLT_MAX      */
+    const float* tgt;               /* fp32 view: B images of C planes of H rows of W              */
+    long long tgt_image_stride;     /* elements; ignored when B == 1                               */
+    long long tgt_channel_stride;   /* elements; ignored when C == 1                               */
+    long long tgt_row_stride;       /* elements, >= W                                              */
+    const float* k_src;             /* device: 3 x 3 row-major intrinsics of the source camera     */
+    long long k_src_image_stride;   /* floats between the matrices of two images; 0: one camera    */
+    float* pose;                    /* device: (B, 3, 4) fp32 [R | t], read and REWRITTEN          */
+    int* status;                    /* device: (B) int, written by nconv_pose_update (apply != 0)  */
+    float* cost;                    /* device: (B, history) fp32                                   */
+    int* n_hist;                    /* device: (B, history) int                                    */
+    int history;                    /* entries of a history row                                    */
+    float huber;                    /* Huber threshold in units of the frames; 0: least squares    */
+    float damping;                  /* A = H + damping diag(H)                                     */
+    int min_points;                 /* >= 6: fewer valid pixels leave the pose as it is (status 1) */
+} nconv_pose_align_desc;
+
+size_t nconv_pose_workspace_bytes(int B, int H, int W);
+int nconv_pose_normal_eq(const struct nconv_pose_align* d, void* workspace, size_t workspace_bytes, void* stream);
+int nconv_pose_update(const struct nconv_pose_align* d, void* workspace, size_t workspace_bytes, int it, int apply,
+                      void* stream);
 
 /* Edge-aware depth smoothness loss and its edge weights (new entry points only: no existing struct or
  * signature changes, so NCONV_ABI_VERSION stays 27). The regulariser the photometric term above is trained

@@ -33,10 +33,13 @@ from . import warp
 from .warp import (PhotometricLoss, ViewWarper, halve_intrinsics, halve_projection, photometric_loss,
                    photometric_ssim_loss, view_warp,
                    warp_projection)
+from . import pose
+from .pose import EstimatePose, PoseEstimator, estimate_pose, pool_sparse, pose_projection, pose_step
 from . import smooth
 from .smooth import EdgeWeights, Smoother, SmoothnessLoss, edge_weights, smoothness_loss
 
-__all__ = ["EdgeWeights", "Smoother", "SmoothnessLoss", "edge_weights", "smoothness_loss", "halve_intrinsics",
+__all__ = ["EstimatePose", "PoseEstimator", "estimate_pose", "pool_sparse", "pose_projection", "pose_step",
+           "EdgeWeights", "Smoother", "SmoothnessLoss", "edge_weights", "smoothness_loss", "halve_intrinsics",
            "halve_projection", "PhotometricLoss", "ViewWarper", "photometric_loss", "photometric_ssim_loss", "view_warp", "warp_projection", "ConfidenceLoss", "ConfLossFn", "confidence_loss", "NearestFill", "NearestFiller", "NearestSample", "nearest_sample",
            "IPBasic", "IPBasicFill", "IPBasicFiller", "ipbasic_fill", "SparsificationCurves", "sparsification","Augment", "Augmenter", "augment","OcclusionFilter", "RemoveOccluded", "remove_occluded","Sparsifier", "SparsifyBatch", "sparsify", "COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
 "LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",

@@ -116,6 +116,9 @@ EXPORTED = (
     "nconv_photo_ssim_workspace_bytes",
     "nconv_photo_ssim_loss_fwd",
     "nconv_photo_ssim_loss_bwd",
+    "nconv_pose_workspace_bytes",
+    "nconv_pose_normal_eq",
+    "nconv_pose_update",
     "nconv_smooth_loss_workspace_bytes",
     "nconv_smooth_loss_fwd",
     "nconv_smooth_loss_bwd",
@@ -307,6 +310,15 @@ class NconvViewWarp(ctypes.Structure):
                 ("z_max", ctypes.c_float)]
 
 
+class NconvPoseAlign(ctypes.Structure):
+    _fields_ = NconvViewWarp._fields_ + [
+        ("tgt", ctypes.c_void_p), ("tgt_image_stride", ctypes.c_longlong), ("tgt_channel_stride", ctypes.c_longlong),
+        ("tgt_row_stride", ctypes.c_longlong), ("k_src", ctypes.c_void_p), ("k_src_image_stride", ctypes.c_longlong),
+        ("pose", ctypes.c_void_p), ("status", ctypes.c_void_p), ("cost", ctypes.c_void_p), ("n_hist", ctypes.c_void_p),
+        ("history", ctypes.c_int), ("huber", ctypes.c_float), ("damping", ctypes.c_float),
+        ("min_points", ctypes.c_int)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -462,6 +474,12 @@ def _declare(lib):
     lib.nconv_photo_ssim_loss_bwd.restype = I
     lib.nconv_photo_ssim_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, F, F, F, P, P, ctypes.c_size_t,
                                               P, P]
+    lib.nconv_pose_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_pose_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_pose_normal_eq.restype = I
+    lib.nconv_pose_normal_eq.argtypes = [ctypes.POINTER(NconvPoseAlign), P, ctypes.c_size_t, P]
+    lib.nconv_pose_update.restype = I
+    lib.nconv_pose_update.argtypes = [ctypes.POINTER(NconvPoseAlign), P, ctypes.c_size_t, I, I, P]
     lib.nconv_smooth_loss_workspace_bytes.restype = ctypes.c_size_t
     lib.nconv_smooth_loss_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_smooth_loss_fwd.restype = I

@@ -886,6 +886,68 @@ int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt,
                     (hipStream_t)stream);
 }
 
+size_t nconv_pose_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::pose_workspace_bytes(B, H, W);
+}
+
+// The descriptor of nconv_pose_* and the workspace checked and turned into the kernels' arguments: the
+// fields it shares with nconv_view_warp by warp_args, tgt as the photometric loss's, then its own.
+static const char* pose_args(const nconv_pose_align* d, const void* ws, size_t ws_bytes, nconv::PoseArgs& a,
+                             std::string& text) {
+    if (!d) return "null descriptor";
+    nconv_view_warp w{};
+    w.B = d->B, w.C = d->C, w.H = d->H, w.W = d->W, w.Hs = d->Hs, w.Ws = d->Ws;
+    w.depth = d->depth, w.depth_image_stride = d->depth_image_stride, w.depth_row_stride = d->depth_row_stride;
+    w.mask = d->mask, w.mask_image_stride = d->mask_image_stride, w.mask_row_stride = d->mask_row_stride;
+    w.src = d->src, w.src_image_stride = d->src_image_stride, w.src_channel_stride = d->src_channel_stride;
+    w.src_row_stride = d->src_row_stride;
+    w.k = d->k, w.k_image_stride = d->k_image_stride, w.m = d->m, w.m_image_stride = d->m_image_stride;
+    w.z_min = d->z_min, w.z_max = d->z_max;
+    a = nconv::PoseArgs{};
+    if (const char* why = warp_args(&w, a.w, text)) return why;
+    if (!d->tgt) return "null tgt";
+    if ((size_t)d->tgt % 4) return "tgt not 4-byte aligned";
+    if (const char* why = warp_image_view("tgt", d->tgt, a.w.B, a.w.C, a.w.H, a.w.W, d->tgt_image_stride,
+                                          d->tgt_channel_stride, d->tgt_row_stride, a.w.tgt, a.w.tcs, text))
+        return why;
+    if (!d->k_src || !d->pose || !d->status || !d->cost || !d->n_hist) return "null k_src, pose, status, cost or n_hist";
+    if ((size_t)d->k_src % 4 || (size_t)d->pose % 4 || (size_t)d->status % 4 || (size_t)d->cost % 4 ||
+        (size_t)d->n_hist % 4)
+        return "k_src / pose / status / cost / n_hist not 4-byte aligned";
+    if (d->k_src_image_stride < 0) return "negative k_src image stride";
+    if (a.w.B > 1 && d->m_image_stride < 12) return "m_image_stride below 12: the update writes one m per image";
+    if (!(d->huber >= 0.f)) return "huber must be >= 0 (and not NaN)";
+    if (!(d->damping >= 0.f)) return "damping must be >= 0 (and not NaN)";
+    if (d->min_points < 6) return "min_points must be at least 6";
+    if (d->history <= 0) return "history must be positive";
+    if (!ws || ws_bytes < nconv::pose_workspace_bytes(a.w.B, a.w.H, a.w.W)) return "workspace too small";
+    if ((size_t)ws % 8) return "workspace not 8-byte aligned";
+    a.k_src = d->k_src, a.ksbs = d->k_src_image_stride;
+    a.pose = d->pose, a.m_out = d->m;
+    a.huber = d->huber, a.damping = d->damping, a.min_points = d->min_points;
+    a.status = d->status, a.cost = d->cost, a.n = d->n_hist, a.history = d->history;
+    return nullptr;
+}
+
+int nconv_pose_normal_eq(const struct nconv_pose_align* d, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_pose_normal_eq";
+    nconv::PoseArgs a;
+    std::string text;
+    if (const char* why = pose_args(d, workspace, workspace_bytes, a, text)) return fail(-22, fn, why);
+    return launched(fn, nconv::launch_pose_normal_eq, a, workspace, (hipStream_t)stream);
+}
+
+int nconv_pose_update(const struct nconv_pose_align* d, void* workspace, size_t workspace_bytes, int it, int apply,
+                      void* stream) {
+    const char* fn = "nconv_pose_update";
+    nconv::PoseArgs a;
+    std::string text;
+    if (const char* why = pose_args(d, workspace, workspace_bytes, a, text)) return fail(-22, fn, why);
+    if (it < 0 || it >= d->history) return fail(-22, fn, "it outside [0, history)");
+    return launched(fn, nconv::launch_pose_update, a, workspace, it, apply, (hipStream_t)stream);
+}
+
 size_t nconv_smooth_loss_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
     return nconv::smooth_loss_workspace_bytes(B, H, W);

@@ -492,6 +492,25 @@ int launch_photo_ssim_loss_fwd(const WarpArgs& a, float alpha, float c1, float c
 int launch_photo_ssim_loss_bwd(const WarpArgs& a, float alpha, float c1, float c2, const float* gloss, const void* ws,
                                float* g_depth, hipStream_t st, const char** why);
 
+// Relative pose by direct image alignment (nconv_pose_normal_eq, nconv_pose_update), pose_align.hip.
+constexpr int kPoseSums = 28;  // 21 of the upper triangle of sum w J^T J, 6 of sum w J r, sum w r^2
+struct PoseArgs {
+    WarpArgs w;               // the warp's operands with tgt; w.m is the fp32 m that the update rewrites
+    const float* k_src;
+    long long ksbs;           // image stride of K_src in floats (0: one camera)
+    float* pose;              // fp32 (B, 3, 4) contiguous: read by normal_eq, rewritten by the update
+    float* m_out;             // w.m as the update writes it
+    float huber, damping;
+    int min_points;
+    int* status;              // (B)
+    float* cost;              // (B, history)
+    int* n;                   // (B, history)
+    int history;
+};
+size_t pose_workspace_bytes(int B, int H, int W);
+int launch_pose_normal_eq(const PoseArgs& a, void* ws, hipStream_t st, const char** why);
+int launch_pose_update(const PoseArgs& a, void* ws, int it, int apply, hipStream_t st, const char** why);
+
 // Edge-aware depth smoothness loss and the edge weights (nconv_smooth_loss_*, nconv_edge_weights), smooth_loss.hip.
 struct SmoothArgs {
     int B, H, W, order;       // order 1: first differences, 2: second differences

@@ -36,8 +36,8 @@ data range R, and the term is clamp((1 - SSIM) / 2, 0, 1) averaged over windows 
 Not offered: a gradient with respect to the source image (a scatter) or to m (poses are inputs); for the SSIM
 term reflection padding, windows other than 3 x 3, a per-pixel error map, the minimum reprojection over
 several sources and auto-masking; a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
-halve_projection(m): dividing k by 2 is wrong by half a pixel), pose estimation. Device tensors
-only: there is no PyTorch path.
+halve_projection(m): dividing k by 2 is wrong by half a pixel). The pose itself is pose.estimate_pose's. Device
+tensors only: there is no PyTorch path.
 """
 import ctypes
 
