@@ -1494,8 +1494,9 @@ int nconv_photo_loss_bwd(const struct nconv_view_warp* d, const float* tgt, long
  * warp of the tile and its halo from the depth: the forward saves no planes, and nothing per-pixel except
  * g_depth reaches memory.
  *
- * NOT offered: reflection padding; windows other than 3 x 3 (no Gaussian window); a per-pixel error map;
- * the minimum reprojection over several sources; auto-masking; a gradient to the images. Whether the SSIM
+ * NOT offered: reflection padding; windows other than 3 x 3 (no Gaussian window); a gradient to the images.
+ * (A per-pixel error map, the minimum reprojection over several sources and auto-masking are
+ * nconv_photo_min_loss_* below.) Whether the SSIM
  * term improves the error on KITTI with this network has not been measured by anyone.
  *
  * workspace: nconv_photo_ssim_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or B * H * W
@@ -1511,6 +1512,88 @@ int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt,
                               long long tgt_channel_stride, long long tgt_row_stride, float alpha, float c1, float c2,
                               const float* gloss, const void* workspace, size_t workspace_bytes, float* g_depth,
                               void* stream);
+
+/* The minimum reprojection over several sources, with auto-masking (new entry points only: no existing struct
+ * or signature changes, so NCONV_ABI_VERSION stays 27): monodepth2's per-pixel minimum of the photometric error
+ * over the previous and the next frame, which Ma et al.'s self-supervised sparse-to-dense also warps from. A
+ * pixel that one neighbouring frame sees occluded, or that left it, takes its error from the frame that does
+ * see it; with auto-masking a pixel whose UNWARPED neighbour already matches the target at least as well (a
+ * standing camera, an object moving with it) adds nothing. The pose side needs nothing new:
+ * nconv_pose_normal_eq / nconv_pose_update are called once per source.
+ *
+ * The rule, fp32, one rounding per operation in the order written, no contraction. Everything not restated
+ * here is nconv_view_warp's and nconv_photo_ssim_loss_*'s rule, bit for bit: valid, the taps, s[ch], the
+ * derivatives, window, the nine-pixel sums, ssim, e[ch], pass, the coefficients a_p, b_p, c_p, c1, c2.
+ *   sources    S sources, 1 <= S <= 4, each with its own src view (of its own size Hs x Ws) and its own m.
+ *              They share depth, mask, k, tgt, z_min, z_max, B, C, H, W. valid_s, window_s, x_s = s_s[ch] are
+ *              those of source s. Per target pixel p and source s:
+ *              tl_s(p) = nconv_photo_loss_fwd's term, the channel sum of |x - y|
+ *              tw_s(p) = termw of the SSIM rule, the channel sum of e[ch]
+ *              comparable_s(p) = alpha == 0 ? valid_s(p) : window_s(p)
+ *              E_s(p) = (alpha * tw_s) + ((1.0f - alpha) * tl_s); at alpha == 0 no window quantity is formed
+ *              and E_s = tl_s
+ *   minimum    best undefined, winner none; for s = 0 .. S - 1 in order, over the comparable sources, source s
+ *              replaces the winner iff winner is none, or E_s < best, or E_s is NaN and best is not. The
+ *              lowest index wins a tie (DETERMINISTIC, where monodepth2 breaks ties by random noise), and a
+ *              NaN stays, as torch.min propagates it. n_c = the number of pixels that have a winner.
+ *   auto-mask  optional; needs Hs == H && Ws == W for every source. I_s(p) is E_s with x replaced by
+ *              src_s[b][ch][i][j] and every pixel of the image taken as valid: defined for every p at
+ *              alpha == 0, and off the image's one-pixel frame otherwise. Imin = the minimum of I_s over ALL S
+ *              sources under the same replacement rule. A pixel with a winner is masked iff Imin <= best (the
+ *              identity wins ties, so two equal frames train nothing; a NaN on either side: not masked).
+ *              n_m = the number of masked pixels; a pixel is kept iff it has a winner and is not masked.
+ *   loss       L = (float)(sum over kept pixels of best / ((double)C * (double)max(n_c, 1)))
+ *              fp32 partials over the same fixed 16 x 64 tiles, in the same lane, wave, tile and image order as
+ *              nconv_photo_loss_fwd (a pixel that is not kept adds +0.0f). The denominator is n_c, NOT the
+ *              kept count: a masked pixel adds nothing to the sum but stays in the mean, which is monodepth2's
+ *              gradient scale and does not jump when the mask flickers. The VALUE differs from monodepth2's,
+ *              which also adds the identity error of the masked pixels as a constant.
+ *   outputs    winner (optional): uint8 (B, H, W), s, 254 for masked, 255 for none
+ *              error (optional): fp32 (B, H, W), kept ? best / (float)C : +0.0f, the per-pixel error map
+ *   backward   den = (float)C * (float)max(n_c, 1)
+ *              kl = (gloss * (1.0f - alpha)) * (1.0f / den)               (gloss NULL: 1)
+ *              kq = (alpha * 0.5f) * (gloss * (1.0f / den))
+ *              for source s and pixel q, SA_s, SB_s, SC_s = the SSIM rule's nine-position sums, in which a
+ *              position p' contributes only if p' is kept, winner(p') == s and the channel passes; otherwise
+ *              it contributes +0.0f
+ *              g_x,s(q)  = -(kq * ((SA_s + (SB_s * x_s,q)) + (SC_s * y_q)));  at alpha == 0 no window quantity
+ *                          is formed and g_x,s = +0.0f
+ *              g_s,ch(q) = ((q kept && winner(q) == s) ? kl * sign(x_s,q - y_q) : +0.0f) + g_x,s(q)
+ *              t_s = valid_s(q) ? nconv_view_warp's channel sum of g_s,ch * ((dIu * du) + (dIv * dv)), with
+ *                    source s's own du, dv : +0.0f
+ *              g_depth(q) = t_0 taken as it is, then + t_1, + t_2, + t_3 in that order
+ *              A pixel that lost to another source still receives the SSIM gradient of neighbouring windows
+ *              that source s won. Every sum is a gather: no atomics, the same bits on every run.
+ * REQUIRED PROPERTIES (finite sums): S = 1 without auto-masking gives, at alpha = 0, L and g_depth equal to
+ * nconv_photo_loss_*'s and, at alpha = 1, equal to nconv_photo_ssim_loss_*'s at alpha = 1. For 0 < alpha < 1
+ * this is a DIFFERENT loss from nconv_photo_ssim_loss_*: one mean over the comparable pixels (those with a
+ * window) instead of two means over n_w and n_v; no equality is claimed there.
+ * Deviations from monodepth2, all on purpose: the one-pixel frame and the all-valid window (no reflection
+ * padding); the denominator n_c; the deterministic tie rule in place of random noise; no identity constant in
+ * the value. Nobody has measured whether minimum reprojection or auto-masking improves the error on KITTI
+ * with this network, and the data loaders hand out no neighbouring frames.
+ *
+ * NOT offered: more than four sources; a per-source weight; a gradient to the images or to m; reflection
+ * padding; an image pyramid (as nconv_view_warp's).
+ *
+ * views: a HOST array of S descriptors. tgt, loss, gloss and g_depth as nconv_photo_loss_*'s. automask: 0 or 1.
+ * workspace: nconv_photo_min_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or B * H * W
+ * >= 2^31); the forward writes it (its first two ints are n_c, n_m; it holds the winner byte plane), the
+ * backward reads it. winner, error: contiguous, either may be NULL. Two launches forward, one backward,
+ * whatever S; no atomics, no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch: everything nconv_photo_ssim_loss_* refuses, for each view ("view s: ..."); S
+ * outside 1..4; views that disagree in B, C, H, W, the depth view, the mask view, k, z_min or z_max; automask
+ * outside {0, 1}, or 1 with a source whose size is not (H, W); a workspace that is NULL, too small or not
+ * 8-byte aligned; a NULL loss or g_depth. */
+size_t nconv_photo_min_workspace_bytes(int B, int H, int W);
+int nconv_photo_min_loss_fwd(const struct nconv_view_warp* views, int S, const float* tgt,
+                             long long tgt_image_stride, long long tgt_channel_stride, long long tgt_row_stride,
+                             float alpha, float c1, float c2, int automask, float* loss, unsigned char* winner,
+                             float* error, void* workspace, size_t workspace_bytes, void* stream);
+int nconv_photo_min_loss_bwd(const struct nconv_view_warp* views, int S, const float* tgt,
+                             long long tgt_image_stride, long long tgt_channel_stride, long long tgt_row_stride,
+                             float alpha, float c1, float c2, int automask, const float* gloss,
+                             const void* workspace, size_t workspace_bytes, float* g_depth, void* stream);
 
 /* Relative camera pose from sparse depth by direct image alignment (new entry points only: no existing struct
  * or signature changes, so NCONV_ABI_VERSION stays 27). The m = K_src . [R | t] that nconv_view_warp_*,

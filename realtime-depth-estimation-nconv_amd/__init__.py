@@ -30,8 +30,8 @@ from . import nearest
 from .nearest import NearestFill, NearestFiller, NearestSample, nearest_sample
 from .train import ConfidenceLoss, ConfLossFn, confidence_loss
 from . import warp
-from .warp import (PhotometricLoss, ViewWarper, halve_intrinsics, halve_projection, photometric_loss,
-                   photometric_ssim_loss, view_warp,
+from .warp import (MinReprojectionLoss, MinReprojector, PhotometricLoss, ViewWarper, halve_intrinsics,
+                   halve_projection, min_reprojection_loss, photometric_loss, photometric_ssim_loss, view_warp,
                    warp_projection)
 from . import pose
 from .pose import EstimatePose, PoseEstimator, estimate_pose, pool_sparse, pose_projection, pose_step
@@ -40,7 +40,7 @@ from .smooth import EdgeWeights, Smoother, SmoothnessLoss, edge_weights, smoothn
 
 __all__ = ["EstimatePose", "PoseEstimator", "estimate_pose", "pool_sparse", "pose_projection", "pose_step",
            "EdgeWeights", "Smoother", "SmoothnessLoss", "edge_weights", "smoothness_loss", "halve_intrinsics",
-           "halve_projection", "PhotometricLoss", "ViewWarper", "photometric_loss", "photometric_ssim_loss", "view_warp", "warp_projection", "ConfidenceLoss", "ConfLossFn", "confidence_loss", "NearestFill", "NearestFiller", "NearestSample", "nearest_sample",
+           "halve_projection", "MinReprojectionLoss", "MinReprojector", "min_reprojection_loss", "PhotometricLoss", "ViewWarper", "photometric_loss", "photometric_ssim_loss", "view_warp", "warp_projection", "ConfidenceLoss", "ConfLossFn", "confidence_loss", "NearestFill", "NearestFiller", "NearestSample", "nearest_sample",
            "IPBasic", "IPBasicFill", "IPBasicFiller", "ipbasic_fill", "SparsificationCurves", "sparsification","Augment", "Augmenter", "augment","OcclusionFilter", "RemoveOccluded", "remove_occluded","Sparsifier", "SparsifyBatch", "sparsify", "COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",
 "LidarProjector", "kitti_projection", "project_points", "projection_from_k", "read_velodyne_bin",
 "PointCloud", "backproject", "backproject_map", "write_ply", "normals", "normal_image", "normals_and_image","EnforcePos", "LayerSpec", "NConv2d", "NConvLayerFn", "nconv_layer", "weight_prep", "DNET",

@@ -116,6 +116,9 @@ EXPORTED = (
     "nconv_photo_ssim_workspace_bytes",
     "nconv_photo_ssim_loss_fwd",
     "nconv_photo_ssim_loss_bwd",
+    "nconv_photo_min_workspace_bytes",
+    "nconv_photo_min_loss_fwd",
+    "nconv_photo_min_loss_bwd",
     "nconv_pose_workspace_bytes",
     "nconv_pose_normal_eq",
     "nconv_pose_update",
@@ -474,6 +477,14 @@ def _declare(lib):
     lib.nconv_photo_ssim_loss_bwd.restype = I
     lib.nconv_photo_ssim_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, L, L, L, F, F, F, P, P, ctypes.c_size_t,
                                               P, P]
+    lib.nconv_photo_min_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_photo_min_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_photo_min_loss_fwd.restype = I
+    lib.nconv_photo_min_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), I, P, L, L, L, F, F, F, I, P, P, P, P,
+                                             ctypes.c_size_t, P]
+    lib.nconv_photo_min_loss_bwd.restype = I
+    lib.nconv_photo_min_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), I, P, L, L, L, F, F, F, I, P, P,
+                                             ctypes.c_size_t, P, P]
     lib.nconv_pose_workspace_bytes.restype = ctypes.c_size_t
     lib.nconv_pose_workspace_bytes.argtypes = [I, I, I]
     lib.nconv_pose_normal_eq.restype = I

@@ -886,6 +886,90 @@ int nconv_photo_ssim_loss_bwd(const struct nconv_view_warp* d, const float* tgt,
                     (hipStream_t)stream);
 }
 
+size_t nconv_photo_min_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
+    return nconv::photo_min_workspace_bytes(B, H, W);
+}
+
+// The S descriptors of nconv_photo_min_loss_*: each by ssim_args (its own "view s: " in front of the reason),
+// then their agreement in everything but the source and its matrix, then auto-masking's equal sizes.
+static const char* min_args(const nconv_view_warp* views, int S, const float* tgt, long long tbs, long long tcs,
+                            long long trs, float alpha, float c1, float c2, int automask, const void* ws,
+                            size_t ws_bytes, nconv::MinArgs& m, std::string& text) {
+    if (S < 1 || S > nconv::kMinSources) return "S must be in 1..4";
+    if (!views) return "null descriptor";
+    if (automask != 0 && automask != 1) return "automask must be 0 or 1";
+    m = nconv::MinArgs{};
+    for (int s = 0; s < S; ++s) {
+        // the workspace's pointer and alignment here; its size, which is this loss's own, below
+        if (const char* why = ssim_args(&views[s], tgt, tbs, tcs, trs, alpha, c1, c2, ws, ~(size_t)0, m.v[s], text)) {
+            text = "view " + std::to_string(s) + ": " + why;
+            return text.c_str();
+        }
+    }
+    const nconv_view_warp& d = views[0];
+    for (int s = 1; s < S; ++s) {
+        const nconv_view_warp& e = views[s];
+        const char* what = nullptr;
+        if (e.B != d.B || e.C != d.C || e.H != d.H || e.W != d.W)
+            what = "B, C, H or W";
+        else if (e.depth != d.depth || e.depth_row_stride != d.depth_row_stride ||
+                 (d.B > 1 && e.depth_image_stride != d.depth_image_stride))
+            what = "the depth view";
+        else if (e.mask != d.mask ||
+                 (d.mask && (e.mask_row_stride != d.mask_row_stride ||
+                             (d.B > 1 && e.mask_image_stride != d.mask_image_stride))))
+            what = "the mask view";
+        else if (e.k != d.k || e.k_image_stride != d.k_image_stride)
+            what = "k";
+        else if (!(e.z_min == d.z_min && e.z_max == d.z_max))
+            what = "z_min or z_max";
+        if (what) {
+            text = "view " + std::to_string(s) + " differs from view 0 in " + what;
+            return text.c_str();
+        }
+    }
+    if (automask)
+        for (int s = 0; s < S; ++s)
+            if (views[s].Hs != d.H || views[s].Ws != d.W) {
+                text = "automask needs sources of the target's size: view " + std::to_string(s) + " is not (H, W)";
+                return text.c_str();
+            }
+    if (ws_bytes < nconv::photo_min_workspace_bytes(d.B, d.H, d.W)) return "workspace too small";
+    m.S = S, m.automask = automask, m.alpha = alpha, m.c1 = c1, m.c2 = c2;
+    return nullptr;
+}
+
+int nconv_photo_min_loss_fwd(const struct nconv_view_warp* views, int S, const float* tgt,
+                             long long tgt_image_stride, long long tgt_channel_stride, long long tgt_row_stride,
+                             float alpha, float c1, float c2, int automask, float* loss, unsigned char* winner,
+                             float* error, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "nconv_photo_min_loss_fwd";
+    nconv::MinArgs m;
+    std::string text;
+    if (const char* why = min_args(views, S, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, alpha, c1, c2,
+                                   automask, workspace, workspace_bytes, m, text))
+        return fail(-22, fn, why);
+    if (!loss) return fail(-22, fn, "null loss");
+    if ((size_t)loss % 4 || (size_t)error % 4) return fail(-22, fn, "loss / error not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_min_loss_fwd, m, loss, winner, error, workspace, (hipStream_t)stream);
+}
+
+int nconv_photo_min_loss_bwd(const struct nconv_view_warp* views, int S, const float* tgt,
+                             long long tgt_image_stride, long long tgt_channel_stride, long long tgt_row_stride,
+                             float alpha, float c1, float c2, int automask, const float* gloss,
+                             const void* workspace, size_t workspace_bytes, float* g_depth, void* stream) {
+    const char* fn = "nconv_photo_min_loss_bwd";
+    nconv::MinArgs m;
+    std::string text;
+    if (const char* why = min_args(views, S, tgt, tgt_image_stride, tgt_channel_stride, tgt_row_stride, alpha, c1, c2,
+                                   automask, workspace, workspace_bytes, m, text))
+        return fail(-22, fn, why);
+    if (!g_depth) return fail(-22, fn, "null g_depth");
+    if ((size_t)gloss % 4 || (size_t)g_depth % 4) return fail(-22, fn, "gloss / g_depth not 4-byte aligned");
+    return launched(fn, nconv::launch_photo_min_loss_bwd, m, gloss, workspace, g_depth, (hipStream_t)stream);
+}
+
 size_t nconv_pose_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W >= (1LL << 31)) return 0;
     return nconv::pose_workspace_bytes(B, H, W);

@@ -491,6 +491,19 @@ int launch_photo_ssim_loss_fwd(const WarpArgs& a, float alpha, float c1, float c
                                hipStream_t st, const char** why);
 int launch_photo_ssim_loss_bwd(const WarpArgs& a, float alpha, float c1, float c2, const float* gloss, const void* ws,
                                float* g_depth, hipStream_t st, const char** why);
+// The minimum of that loss's per-pixel error over several sources, with auto-masking
+// (nconv_photo_min_loss_*), photo_min.hip.
+constexpr int kMinSources = 4;
+struct MinArgs {
+    WarpArgs v[kMinSources];  // the S sources with tgt; they differ in src, scs, Hs, Ws, m and mbs alone
+    int S, automask;          // automask 0 / 1; 1 needs Hs == H and Ws == W for every source
+    float alpha, c1, c2;
+};
+size_t photo_min_workspace_bytes(int B, int H, int W);
+int launch_photo_min_loss_fwd(const MinArgs& m, float* loss, unsigned char* winner, float* error, void* ws,
+                              hipStream_t st, const char** why);
+int launch_photo_min_loss_bwd(const MinArgs& m, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
+                              const char** why);
 
 // Relative pose by direct image alignment (nconv_pose_normal_eq, nconv_pose_update), pose_align.hip.
 constexpr int kPoseSums = 28;  // 21 of the upper triangle of sum w J^T J, 6 of sum w J r, sum w r^2

@@ -28,18 +28,16 @@
 // 1.4 KB, one channel's a, b, c 14.3 KB), both below 64 KB. The image comes from blockIdx alone, so K, m and
 // the planes' buffer resources stay wave-uniform; an invalid pixel loads no tap and no tgt; no byte outside
 // a view is read. No atomics, no host synchronisation, no allocation: capturable, the same bits on every run.
-#include "warp_common.h"
+//
+// The window pieces (the regions, stage_pixel, window_valid, ssim_window, ssim_term, ssim_coef) are
+// ssim_common.h's, shared with photo_min.hip.
+#include "ssim_common.h"
 
 namespace nconv {
 
 namespace {
 
 constexpr int kSsimF = 1024;                             // finalize: sixteen waves, one image each at a time
-constexpr int kFH = kLossTH + 2, kFW = kLossTW + 2;      // the forward's region: the tile and a one-pixel halo
-constexpr int kFN = kFH * kFW;
-constexpr int kGH = kLossTH + 4, kGW = kLossTW + 4;      // the backward's region: a two-pixel halo
-constexpr int kGN = kGH * kGW;
-
 // the workspace: n_v, n_w first (the backward and the caller read them there); [.][0] L1, [.][1] SSIM
 struct SsimWs {
     int* n;        // [2]: n_v, n_w
@@ -56,69 +54,6 @@ __host__ __device__ SsimWs ssim_ws(void* ws, int B, int tiles) {
     p.part = (float*)(p.icnt + 2 * (size_t)B);
     p.cnt = (int*)(p.part + 2 * (size_t)B * tiles);
     return p;
-}
-
-// x, y (every channel) and validity of region pixel idx of an RH x RW region whose corner is (i0, j0)
-template <int C, int RW, int RN>
-__device__ __forceinline__ void stage_pixel(const WarpArgs& a, const Camera& cam, const Proj& q, int b, int i0,
-                                            int j0, int idx, float (&sx)[C][RN], float (&sy)[C][RN],
-                                            unsigned char (&sv)[RN]) {
-    const int i = i0 + idx / RW, j = j0 + idx % RW;
-    const bool inside = i >= 0 && i < a.H && j >= 0 && j < a.W;
-    const Geo g = warp_geometry(a, cam, q, b, i, j, inside);
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) {
-        sx[ch][idx] = warp_sample(a, g, b, ch).s;
-        sy[ch][idx] = tgt_load(a, b, ch, i, j, g.ok);
-    }
-    sv[idx] = g.ok ? 1 : 0;
-}
-
-// all nine pixels of the window centred at o are valid
-template <int RW>
-__device__ __forceinline__ bool window_valid(const unsigned char* sv, int o) {
-    bool w = true;
-#pragma unroll
-    for (int di = -1; di <= 1; ++di)
-#pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) w = w && sv[o + di * RW + dj] != 0;
-    return w;
-}
-
-// SSIM of the window centred at o
-struct Ssim {
-    float mux, muy, A1, A2, B1, B2, den, ssim, t;
-};
-template <int RW>
-__device__ __forceinline__ Ssim ssim_window(const float* x, const float* y, int o, float c1, float c2) {
-#pragma clang fp contract(off)
-    float Sx = 0.f, Sy = 0.f, Sxx = 0.f, Syy = 0.f, Sxy = 0.f;
-#pragma unroll
-    for (int di = -1; di <= 1; ++di) {
-#pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) {
-            const float xv = x[o + di * RW + dj], yv = y[o + di * RW + dj];
-            const float xx = xv * xv, yy = yv * yv, xy = xv * yv;
-            const bool first = di == -1 && dj == -1;
-            Sx = first ? xv : Sx + xv, Sy = first ? yv : Sy + yv;
-            Sxx = first ? xx : Sxx + xx, Syy = first ? yy : Syy + yy, Sxy = first ? xy : Sxy + xy;
-        }
-    }
-    Ssim s;
-    s.mux = Sx / 9.0f, s.muy = Sy / 9.0f;
-    const float mxx = s.mux * s.mux, myy = s.muy * s.muy, mxy = s.mux * s.muy;
-    const float exx = Sxx / 9.0f, eyy = Syy / 9.0f, exy = Sxy / 9.0f;
-    const float vx = exx - mxx, vy = eyy - myy, vxy = exy - mxy;
-    const float m2 = 2.0f * mxy, v2 = 2.0f * vxy;
-    s.A1 = m2 + c1, s.A2 = v2 + c2;
-    const float ms = mxx + myy, vs = vx + vy;
-    s.B1 = ms + c1, s.B2 = vs + c2;
-    const float num = s.A1 * s.A2;
-    s.den = s.B1 * s.B2;
-    s.ssim = num / s.den;
-    const float d = 1.0f - s.ssim;
-    s.t = d * 0.5f;
-    return s;
 }
 
 // one workgroup per tile; part[2 tile + k] and cnt[2 tile + k], k = 0: L1 and n_v, 1: SSIM and n_w
@@ -151,7 +86,7 @@ __global__ __launch_bounds__(kWT) void ssim_partials(WarpArgs a, float c1, float
             const float e = fabsf(sx[ch][at] - sy[ch][at]);
             term = ch == 0 ? e : term + e;
             const Ssim s = ssim_window<kFW>(sx[ch], sy[ch], at, c1, c2);
-            const float ew = s.t < 0.f ? 0.f : s.t > 1.f ? 1.f : s.t;
+            const float ew = ssim_term(s);
             termw = ch == 0 ? ew : termw + ew;
         }
         s1 += ok ? term : 0.f;
@@ -229,19 +164,8 @@ __global__ __launch_bounds__(kWT) void ssim_grad(WarpArgs a, float alpha, float 
             const int at = (idx / kFW + 1) * kGW + idx % kFW + 1;  // the window's centre in the 20 x 68 region
             const Ssim s = ssim_window<kGW>(sx[ch], sy[ch], at, c1, c2);
             const bool pass = window_valid<kGW>(sv, at) && s.t >= 0.f && s.t <= 1.f;
-            const float c_n = 2.0f * s.A1, d9 = 9.0f * s.den;
-            const float cp = c_n / d9;
-            const float b_n = 2.0f * s.ssim, b_d = 9.0f * s.B2;
-            const float bq = b_n / b_d;
-            const float sm = s.ssim * s.mux;
-            const float dA = s.A2 - s.A1;
-            const float p1n = s.muy * dA;
-            const float p1 = p1n / s.den, p2 = sm / s.B1, p3 = sm / s.B2;
-            const float p12 = p1 - p2;
-            const float p123 = p12 + p3;
-            const float a2 = 2.0f * p123;
-            const float ap = a2 / 9.0f;
-            wa[idx] = pass ? ap : 0.f, wb[idx] = pass ? -bq : 0.f, wc[idx] = pass ? cp : 0.f;
+            const SsimCoef k = ssim_coef(s);
+            wa[idx] = pass ? k.a : 0.f, wb[idx] = pass ? k.b : 0.f, wc[idx] = pass ? k.c : 0.f;
         }
         __syncthreads();
 #pragma unroll 1

@@ -1,5 +1,6 @@
 // warp_common.h — the per-pixel pieces of the depth-driven view warp, shared by view_warp.hip (the warp, its
-// gradient, the L1 photometric loss) and photo_ssim.hip (the SSIM + L1 loss): the projection of a target
+// gradient, the L1 photometric loss), photo_ssim.hip (the SSIM + L1 loss) and photo_min.hip (its minimum over
+// several sources): the projection of a target
 // pixel into the source frame, its four taps and their blend, the derivatives of that with respect to the
 // depth, and the thread map of the 16 x 64 tile. The rule is stated operation by operation in
 // include/nconv.h (nconv_view_warp_*); every operation here is fp32 in that order, no contraction.

@@ -15,7 +15,11 @@ to the current frame, and let the gradient flow into the depth.
   photometric_ssim_loss  alpha / 2 (1 - SSIM) + (1 - alpha) L1, the loss the monodepth family trains with, over
                       3 x 3 windows of all-valid pixels, the warp fused in (nconv_photo_ssim_loss_fwd / _bwd:
                       two launches forward, one backward; neither warped nor any SSIM plane reaches memory)
-  PhotometricLoss     either loss as an nn.Module (alpha = 0: the L1 path)
+  min_reprojection_loss  monodepth2's per-pixel minimum of that loss's error over 1..4 sources, with auto-masking,
+                      an optional winner plane and per-pixel error map (nconv_photo_min_loss_fwd / _bwd: two
+                      launches forward, one backward, whatever the number of sources)
+  MinReprojectionLoss, MinReprojector  its nn.Module and its variant with kept buffers (hipGraph capture)
+  PhotometricLoss     either single-source loss as an nn.Module (alpha = 0: the L1 path)
   ViewWarper          the same with outputs and workspace kept between calls (hipGraph capture)
   halve_intrinsics    k of a half-resolution pyramid level made by 2 x 2 average pooling
   halve_projection    m of that level
@@ -33,9 +37,13 @@ ReflectionPad2d(1), on purpose: a term counts where all its pixels count, as in 
 and the covariance are monodepth's E[xy] - E[x] E[y] over the window, c1 = (0.01 R)^2, c2 = (0.03 R)^2 for the
 data range R, and the term is clamp((1 - SSIM) / 2, 0, 1) averaged over windows and channels.
 
+The minimum over several sources (include/nconv.h, nconv_photo_min_loss_*): per pixel the smallest of the
+sources' errors alpha termw + (1 - alpha) term over the sources in which the pixel has a window, the lowest
+index winning a tie; with auto-masking a pixel whose best unwarped source matches at least as well adds nothing
+to the sum but stays in the mean over the pixels with a winner.
+
 Not offered: a gradient with respect to the source image (a scatter) or to m (poses are inputs); for the SSIM
-term reflection padding, windows other than 3 x 3, a per-pixel error map, the minimum reprojection over
-several sources and auto-masking; a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
+term reflection padding and windows other than 3 x 3; a built-in image pyramid (a level is F.avg_pool2d(., 2) of the frames and the depth with halve_intrinsics(k) and
 halve_projection(m): dividing k by 2 is wrong by half a pixel). The pose itself is pose.estimate_pose's. Device
 tensors only: there is no PyTorch path.
 """
@@ -431,3 +439,171 @@ class ViewWarper:
             return r[:2] if return_valid_count else r
         return photometric_loss(depth, k, tgt, src, m, mask, self.z_min, self.z_max, return_valid_count,
                                 out=self._loss)
+
+
+# ------------------------------------------------------------------------------------------------
+# the minimum reprojection over several sources, with auto-masking (nconv_photo_min_loss_*)
+# ------------------------------------------------------------------------------------------------
+MAX_SOURCES = 4
+WINNER_MASKED, WINNER_NONE = 254, 255
+
+
+def _min_descriptors(depth, k, tgt, srcs, ms, mask, z_min, z_max, automask):
+    """The S checked descriptors as a ctypes array, (B, C, H, W), tgt's strides and the mask as passed on."""
+    from . import _lib
+    if torch.is_tensor(srcs) or torch.is_tensor(ms):
+        raise TypeError(f"{PREFIX}: srcs and ms must be sequences of 1..{MAX_SOURCES} tensors, not tensors")
+    srcs, ms = list(srcs), list(ms)
+    if not 1 <= len(srcs) <= MAX_SOURCES or len(ms) != len(srcs):
+        raise ValueError(f"{PREFIX}: need 1..{MAX_SOURCES} sources and as many matrices, got {len(srcs)} srcs and "
+                         f"{len(ms)} ms")
+    if automask and torch.is_tensor(depth) and depth.dim() == 4:  # shapes before devices, as _descriptor does
+        H, W = depth.shape[2:]
+        for s, src in enumerate(srcs):
+            if torch.is_tensor(src) and src.dim() == 4 and tuple(src.shape[2:]) != (H, W):
+                raise ValueError(f"{PREFIX}: automask compares the unwarped sources with tgt, so every source must "
+                                 f"be {H} x {W}; srcs[{s}] is {src.shape[2]} x {src.shape[3]} (pass automask=False)")
+    descs, shape, tstr, mview = [], None, None, None
+    for src, m in zip(srcs, ms):
+        d, shape, tstr, mview = _descriptor(depth, k, src, m, mask, z_min, z_max, tgt)
+        descs.append(d)
+    return (_lib.NconvViewWarp * len(descs))(*descs), shape, tstr, mview
+
+
+def min_workspace_bytes(B, H, W):
+    """Bytes of min_reprojection_loss's workspace (nconv_photo_min_workspace_bytes); its first two int32 are n_c
+    and n_m, and it holds the winner byte plane the backward reads."""
+    from . import _lib
+    B, H, W = int(B), int(H), int(W)
+    if B <= 0 or H <= 0 or W <= 0 or B * H * W >= 2 ** 31:
+        raise ValueError(f"{PREFIX}: a batch of (B, H, W) = {(B, H, W)} is empty or too large (B * H * W < 2^31)")
+    return _lib.lib().nconv_photo_min_workspace_bytes(B, H, W)
+
+
+class MinReprojectionLossFn(torch.autograd.Function):
+    """min_reprojection_loss's kernels (nconv_photo_min_loss_fwd / _bwd); the gradient reaches the depth alone."""
+
+    @staticmethod
+    def forward(ctx, depth, k, tgt, mask, consts, automask, z_min, z_max, want, out, S, *srcs_ms):
+        from . import _lib
+        srcs, ms = srcs_ms[:S], srcs_ms[S:]
+        views, (B, C, H, W), t, mask = _min_descriptors(depth, k, tgt, srcs, ms, mask, z_min, z_max, automask)
+        dev = depth.device
+        nbytes = min_workspace_bytes(B, H, W)
+        ws = _views.output(out, "workspace", (nbytes,), torch.uint8, dev, PREFIX, source="depth")
+        loss = _views.output(out, "loss", (), torch.float32, dev, PREFIX, source="depth")
+        winner = _views.output(out, "winner", (B, H, W), torch.uint8, dev, PREFIX, source="depth") if want[0] else None
+        error = _views.output(out, "error", (B, H, W), torch.float32, dev, PREFIX, source="depth") if want[1] else None
+        rc = _lib.lib().nconv_photo_min_loss_fwd(views, S, _lib.ptr(tgt), t[0], t[1], t[2], *consts, int(automask),
+                                                 _lib.ptr(loss), _lib.ptr(winner), _lib.ptr(error), _lib.ptr(ws),
+                                                 nbytes, _lib.stream_handle(dev))
+        _lib.check(rc, "nconv_photo_min_loss_fwd")
+        ctx.z, ctx.consts, ctx.automask, ctx.S = (z_min, z_max), consts, automask, S
+        ctx.g_depth = None if out is None else out.get("g_depth")
+        ctx.save_for_backward(depth, k, tgt, mask, ws, *srcs_ms)
+        n = ws[:8].view(torch.int32)
+        n_c, n_m = n[0], n[1]
+        ctx.mark_non_differentiable(*(x for x in (n_c, n_m, winner, error) if x is not None))
+        return loss, n_c, n_m, winner, error
+
+    @staticmethod
+    def backward(ctx, gloss, *_):
+        from . import _lib
+        depth, k, tgt, mask, ws, *srcs_ms = ctx.saved_tensors
+        S = ctx.S
+        views, (B, C, H, W), t, _ = _min_descriptors(depth, k, tgt, srcs_ms[:S], srcs_ms[S:], mask, *ctx.z,
+                                                     ctx.automask)
+        gloss = gloss.contiguous()
+        g = ctx.g_depth if ctx.g_depth is not None else torch.empty((B, 1, H, W), dtype=torch.float32,
+                                                                    device=depth.device)
+        rc = _lib.lib().nconv_photo_min_loss_bwd(views, S, _lib.ptr(tgt), t[0], t[1], t[2], *ctx.consts,
+                                                 int(ctx.automask), _lib.ptr(gloss), _lib.ptr(ws), ws.numel(),
+                                                 _lib.ptr(g), _lib.stream_handle(depth.device))
+        _lib.check(rc, "nconv_photo_min_loss_bwd")
+        return (g,) + (None,) * (10 + 2 * S)
+
+
+def min_reprojection_loss(depth, k, tgt, srcs, ms, mask=None, alpha=0.85, data_range=255.0, automask=True,
+                          z_min=0.0, z_max=None, return_counts=False, return_winner=False, return_error=False,
+                          out=None):
+    """monodepth2's loss over several source frames: per pixel the SMALLEST of E_s = alpha termw_s + (1 - alpha)
+    term_s over the sources in which the pixel is comparable (has a window; at alpha = 0: is valid), termw_s and
+    term_s the per-pixel channel sums of photometric_ssim_loss's and photometric_loss's terms; the lowest index
+    wins a tie. automask: a pixel whose best UNWARPED source matches tgt at least as well (Imin <= best) is
+    masked: it adds nothing to the sum but stays in the mean, L = sum over kept pixels of best / (C max(n_c, 1)),
+    n_c the pixels with a winner (every source must then have tgt's size). A scalar on the device, followed, as
+    asked for, by (n_c, n_m) (return_counts: int32 views of the workspace, n_m the masked pixels), winner
+    (return_winner: uint8 (B, H, W), the source's index, 254 masked, 255 none) and error (return_error: fp32
+    (B, H, W), best / C of a kept pixel, else 0: the per-pixel error map, ready for colorize). srcs, ms: sequences
+    of 1..4 tensors, each as photometric_ssim_loss's src and m (a source may have its own size); the other
+    operands as photometric_ssim_loss's; differentiable in depth only. out: an optional dict of kept contiguous
+    buffers 'workspace' (uint8, min_workspace_bytes(B, H, W)), 'loss', 'g_depth' (B, 1, H, W), 'winner', 'error'.
+    Two launches forward, one backward, whatever the number of sources. With one source and no auto-masking the
+    loss and the gradient equal photometric_loss's at alpha = 0 and photometric_ssim_loss's at alpha = 1; in
+    between this is a different loss (one mean over the pixels with a window, not two means)."""
+    consts = _ssim_constants(alpha, data_range)
+    srcs, ms = list(srcs), list(ms)
+    if len(ms) != len(srcs):
+        raise ValueError(f"{PREFIX}: need as many matrices as sources, got {len(srcs)} srcs and {len(ms)} ms")
+    loss, n_c, n_m, winner, error = MinReprojectionLossFn.apply(
+        depth, k, tgt, mask, consts, bool(automask), z_min, z_max, (bool(return_winner), bool(return_error)), out,
+        len(srcs), *srcs, *ms)
+    res = (loss,) + ((n_c, n_m) if return_counts else ()) + ((winner,) if return_winner else ()) \
+        + ((error,) if return_error else ())
+    return res if len(res) > 1 else loss
+
+
+class MinReprojectionLoss(torch.nn.Module):
+    """min_reprojection_loss with its constants held: loss(depth, k, tgt, srcs, ms, mask=None). In a training
+    step: calculate_loss(pred, gt, True) + w * loss(pred, k, rgb, (rgb_prev, rgb_next), (m_prev, m_next)), the ms
+    refilled in place per batch (GraphedTrainStep inputs). alpha, data_range and automask are Python values,
+    constants of a capture."""
+
+    def __init__(self, alpha=0.85, automask=True, data_range=255.0, z_min=0.0, z_max=None):
+        super().__init__()
+        if not float(z_min) >= 0.0 or (z_max is not None and not float(z_max) >= float(z_min)):
+            raise ValueError(f"{PREFIX}: need 0 <= z_min <= z_max, got z_min={z_min}, z_max={z_max}")
+        self.z_min, self.z_max = float(z_min), None if z_max is None else float(z_max)
+        self.alpha, _, _ = _ssim_constants(alpha, data_range)
+        self.data_range, self.automask = float(data_range), bool(automask)
+
+    def forward(self, depth, k, tgt, srcs, ms, mask=None):
+        return min_reprojection_loss(depth, k, tgt, srcs, ms, mask, self.alpha, self.data_range, self.automask,
+                                     self.z_min, self.z_max)
+
+
+class MinReprojector:
+    """min_reprojection_loss for fixed sizes with its workspace, loss, gradient, winner and error buffers kept
+    between calls: no allocation after construction, so the calls can be captured with torch.cuda.graph and
+    replayed on operands refilled in place (ViewWarper's sibling). reproj(depth, k, tgt, srcs, ms) -> loss, or the
+    tuple min_reprojection_loss returns with return_counts / return_winner / return_error. The returned tensors
+    are the kept ones, overwritten by the next call."""
+
+    def __init__(self, size, S=2, B=1, C=3, device=None, alpha=0.85, data_range=255.0, automask=True, z_min=0.0,
+                 z_max=None):
+        H, W = (int(v) for v in size)
+        if min(H, W, int(B)) <= 0 or int(C) not in (1, 3) or not 1 <= int(S) <= MAX_SOURCES:
+            raise ValueError(f"{PREFIX}: sizes must be positive, C 1 or 3 and S in 1..{MAX_SOURCES}, got {size}, "
+                             f"S={S}, B={B}, C={C}")
+        self.size, self.S, self.B, self.C = (H, W), int(S), int(B), int(C)
+        self.z_min, self.z_max = z_min, z_max
+        self.alpha, _, _ = _ssim_constants(alpha, data_range)
+        self.data_range, self.automask = float(data_range), bool(automask)
+        dev = torch.device("cuda" if device is None else device)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._out = {"workspace": torch.empty(min_workspace_bytes(self.B, H, W), dtype=torch.uint8, device=dev),
+                     "loss": torch.empty((), **f32), "g_depth": torch.empty(self.B, 1, H, W, **f32),
+                     "winner": torch.empty(self.B, H, W, dtype=torch.uint8, device=dev),
+                     "error": torch.empty(self.B, H, W, **f32)}
+
+    def __call__(self, depth, k, tgt, srcs, ms, mask=None, return_counts=False, return_winner=False,
+                 return_error=False):
+        srcs = list(srcs)
+        if torch.is_tensor(depth) and depth.dim() == 4 and torch.is_tensor(tgt) and tgt.dim() == 4:
+            got = (depth.shape[0], tgt.shape[1], tuple(depth.shape[2:]), len(srcs))
+            if got != (self.B, self.C, self.size, self.S):
+                raise ValueError(f"{PREFIX}: MinReprojector was built for B={self.B}, C={self.C}, {self.size}, "
+                                 f"S={self.S}; got B={got[0]}, C={got[1]}, {got[2]}, S={got[3]}")
+        return min_reprojection_loss(depth, k, tgt, srcs, ms, mask, self.alpha, self.data_range, self.automask,
+                                     self.z_min, self.z_max, return_counts, return_winner, return_error,
+                                     out=self._out)
