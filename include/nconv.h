@@ -1595,6 +1595,87 @@ int nconv_photo_min_loss_bwd(const struct nconv_view_warp* views, int S, const f
                              float alpha, float c1, float c2, int automask, const float* gloss,
                              const void* workspace, size_t workspace_bytes, float* g_depth, void* stream);
 
+/* Cross-view depth consistency: the check with fusion, and the geometry-consistency loss (new entry points
+ * only: no existing struct or signature changes, so NCONV_ABI_VERSION stays 27). Everything above uses a
+ * neighbouring frame through its colours; these compare the DEPTH of two views. nconv_depth_consistency is the
+ * geometric check of MVSNet's filter_depth and COLMAP's fusion: project a target pixel into the neighbour, read
+ * the neighbour's depth there, carry that point back, and keep the pixel only if it lands where it started, at
+ * the depth it started with; the kept pixels' depths are averaged over the views that agree.
+ * nconv_geo_consistency_loss_* is the geometry-consistency term of SC-SfMLearner (Bian et al., NeurIPS 2019),
+ * which ties the scale of consecutive predictions together and whose per-pixel map is the usual occlusion /
+ * moving-object mask of the photometric losses.
+ *
+ * The rule, fp32, one rounding per operation in the order written, no contraction. For each target pixel
+ * (b, i, j) with z = depth[b][i][j], and each source s = 0 .. S - 1 in order (1 <= S <= 4):
+ *   descriptor  source s is a struct nconv_view_warp whose src is the source view's DEPTH plane (C == 1), k the
+ *               target intrinsics and m = K_s . [R | t]; the S descriptors share B, H, W, the depth view, the
+ *               mask view, k, z_min and z_max. A struct nconv_consistency_source adds two device matrices, each
+ *               with an image stride (0: shared by the batch): k_src, 3 x 3 row-major, of which
+ *               fxs, fys, cxs, cys = [0][0], [1][1], [0][2], [1][2] are read as k's are; m_back, 3 x 4 row-major,
+ *               K_tgt . [R | t]^-1, which takes the source camera frame to target pixels.
+ *   projection  pvalid, valid, u, v, c, the taps a00 .. a11, the weights and the blend s (here zs) are
+ *               nconv_view_warp's, bit for bit, the optional target mask and z_min / z_max included.
+ *   tvalid      every one of the four taps t satisfies t > z_min && t <= z_max (written this way so that a NaN
+ *               or the 0 of a hole of a sparse plane is not valid): a blend is never taken across an invalid tap
+ *   point       xs = ((u - cxs) * zs) / fxs          ys = ((v - cys) * zs) / fys
+ *   way back    a2 = dot(m_back[0], (xs, ys, zs))    likewise b2 (row 1) and c2 (row 2)   (nconv_lidar_project's dot)
+ *               u2 = a2 / c2       v2 = b2 / c2       z2 = c2
+ *   errors      du = u2 - (float)j                   dv = v2 - (float)i
+ *               d2 = (du * du) + (dv * dv)           rz = fabsf(z2 - z)           tol2 = px_tol * px_tol
+ *   decision    cons_s = valid && tvalid && c2 > 0 && d2 <= tol2 && rz <= rel_tol * z
+ *               float comparisons: a NaN is not consistent
+ *   fusion      n = the number of consistent sources; acc = z, then acc = acc + z2_s for the consistent
+ *               sources in index order; fused = (pvalid && n >= min_views) ? acc / (float)(n + 1) : +0.0f
+ *               (0 <= min_views <= S; at min_views == 0 a valid pixel without a consistent source keeps z)
+ *   outputs     fused (B, H, W) fp32; count (B, H, W) uint8 = n; views (B, H, W) uint8, bit s = cons_s;
+ *               reproj and reldiff (B, S, H, W) fp32 = d2 and rz / z, +inf where !(valid && tvalid && c2 > 0),
+ *               so that a threshold on them is false there. Each may be NULL (skipped), not all.
+ * The loss takes ONE source and nothing from m_back or k_src. On the pixels with valid && tvalid (counted):
+ *               num = c - zs          den = c + zs          diff = fabsf(num) / den
+ *               L = (sum diff) / max(n_g, 1),   n_g the counted pixels, an integer counted on the device
+ *   c is the point's depth in the source camera only when the third row of K_src is (0 0 1); the loaders'
+ *   matrices satisfy this, and it is NOT checked on the device.
+ *   backward    sg  = num > 0 ? 1 : num < 0 ? -1 : 0
+ *               dc  = c' of nconv_view_warp's derivatives
+ *               dzs = (dIu * du) + (dIv * dv), nconv_view_warp's dIu, dIv, du, dv taken on the depth taps
+ *               kk  = gloss * (1.0f / (float)max(n_g, 1))                               (gloss NULL: 1)
+ *               g_depth = (kk * sg) * ((((dc - dzs) * den) - (num * (dc + dzs))) / (den * den)),
+ *               +0.0f off the counted pixels. A gather: no atomics, the same bits on every run.
+ * The sum is nconv_photo_loss_fwd's tree: fp32 partials over fixed 16 x 64 tiles, tiles and images combined in
+ * double in a fixed order, divided by max(n_g, 1) in double and rounded to fp32 once; the count is exact and
+ * left in the first int of the workspace for the backward: no host synchronisation.
+ *
+ * NOT offered: a gradient with respect to the source depth (a scatter) or to the pose; confidence-weighted
+ * averaging; per-image kept counts; more than four sources. The symmetric loss of the paper is two calls with
+ * the roles and the pose swapped. The defaults callers use (px_tol 1, rel_tol 0.01, min_views 1) are MVSNet's
+ * convention; nobody has measured them on KITTI with this network. An invalid pixel loads no tap, a valid one
+ * reads taps inside the source plane by the clamps: no byte outside a view's extent is read.
+ *
+ * views, sources: HOST arrays of S entries. fused, count, views_out, reproj, reldiff: contiguous. One launch
+ * whatever S. loss, gloss: device scalars; diff: (B, H, W) fp32 contiguous, the per-pixel term, +0.0f where not
+ * counted, or NULL; g_depth: (B, H, W) fp32 contiguous, OVERWRITTEN. workspace:
+ * nconv_geo_consistency_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: B, H or W <= 0 or B * H * W >= 2^31).
+ * Two launches forward, one backward; no atomics, no host synchronisation, no allocation: capturable.
+ * -EINVAL before any launch: everything nconv_view_warp_* refuses, for each view ("view s: ..."); C != 1; S
+ * outside 1..4; a NULL k_src or m_back, or a negative image stride of either; views that disagree in what they
+ * share; px_tol or rel_tol negative or NaN; min_views outside 0..S; no output at all; B * S * H * W >= 2^31; for
+ * the loss a NULL loss or g_depth, and a workspace that is NULL, too small or not 8-byte aligned. */
+typedef struct nconv_consistency_source {
+    const float* k_src;             /* device: 3 x 3 row-major intrinsics of the source camera     */
+    long long k_src_image_stride;   /* floats between the matrices of two images; 0: one camera    */
+    const float* m_back;            /* device: 3 x 4 row-major K_tgt . [R | t]^-1                  */
+    long long m_back_image_stride;  /* floats between the matrices of two images; 0: one matrix    */
+} nconv_consistency_source_desc;
+
+int nconv_depth_consistency(const struct nconv_view_warp* views, const struct nconv_consistency_source* sources,
+                            int S, float px_tol, float rel_tol, int min_views, float* fused, unsigned char* count,
+                            unsigned char* views_out, float* reproj, float* reldiff, void* stream);
+size_t nconv_geo_consistency_workspace_bytes(int B, int H, int W);
+int nconv_geo_consistency_loss_fwd(const struct nconv_view_warp* d, float* loss, float* diff, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int nconv_geo_consistency_loss_bwd(const struct nconv_view_warp* d, const float* gloss, const void* workspace,
+                                   size_t workspace_bytes, float* g_depth, void* stream);
+
 /* Relative camera pose from sparse depth by direct image alignment (new entry points only: no existing struct
  * or signature changes, so NCONV_ABI_VERSION stays 27). The m = K_src . [R | t] that nconv_view_warp_*,
  * nconv_photo_loss_* and nconv_photo_ssim_loss_* take as an input, estimated from what a training batch holds:

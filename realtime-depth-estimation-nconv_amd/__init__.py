@@ -37,8 +37,12 @@ from . import pose
 from .pose import EstimatePose, PoseEstimator, estimate_pose, pool_sparse, pose_projection, pose_step
 from . import smooth
 from .smooth import EdgeWeights, Smoother, SmoothnessLoss, edge_weights, smoothness_loss
+from . import consistency
+from .consistency import (DepthFuser, GeometryConsistency, GeometryConsistencyLoss, depth_consistency,
+                          geometry_consistency_loss, inverse_pose)
 
-__all__ = ["EstimatePose", "PoseEstimator", "estimate_pose", "pool_sparse", "pose_projection", "pose_step",
+__all__ = ["DepthFuser", "GeometryConsistency", "GeometryConsistencyLoss", "depth_consistency",
+           "geometry_consistency_loss", "inverse_pose", "EstimatePose", "PoseEstimator", "estimate_pose", "pool_sparse", "pose_projection", "pose_step",
            "EdgeWeights", "Smoother", "SmoothnessLoss", "edge_weights", "smoothness_loss", "halve_intrinsics",
            "halve_projection", "MinReprojectionLoss", "MinReprojector", "min_reprojection_loss", "PhotometricLoss", "ViewWarper", "photometric_loss", "photometric_ssim_loss", "view_warp", "warp_projection", "ConfidenceLoss", "ConfLossFn", "confidence_loss", "NearestFill", "NearestFiller", "NearestSample", "nearest_sample",
            "IPBasic", "IPBasicFill", "IPBasicFiller", "ipbasic_fill", "SparsificationCurves", "sparsification","Augment", "Augmenter", "augment","OcclusionFilter", "RemoveOccluded", "remove_occluded","Sparsifier", "SparsifyBatch", "sparsify", "COLORMAPS", "Colorizer", "colorize", "overlay", "write_png8",

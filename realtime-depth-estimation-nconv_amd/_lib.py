@@ -126,6 +126,10 @@ EXPORTED = (
     "nconv_smooth_loss_fwd",
     "nconv_smooth_loss_bwd",
     "nconv_edge_weights",
+    "nconv_depth_consistency",
+    "nconv_geo_consistency_workspace_bytes",
+    "nconv_geo_consistency_loss_fwd",
+    "nconv_geo_consistency_loss_bwd",
 )
 
 
@@ -311,6 +315,11 @@ class NconvViewWarp(ctypes.Structure):
                 ("src_row_stride", ctypes.c_longlong), ("k", ctypes.c_void_p), ("k_image_stride", ctypes.c_longlong),
                 ("m", ctypes.c_void_p), ("m_image_stride", ctypes.c_longlong), ("z_min", ctypes.c_float),
                 ("z_max", ctypes.c_float)]
+
+
+class NconvConsistencySource(ctypes.Structure):
+    _fields_ = [("k_src", ctypes.c_void_p), ("k_src_image_stride", ctypes.c_longlong),
+                ("m_back", ctypes.c_void_p), ("m_back_image_stride", ctypes.c_longlong)]
 
 
 class NconvPoseAlign(ctypes.Structure):
@@ -499,6 +508,15 @@ def _declare(lib):
     lib.nconv_smooth_loss_bwd.argtypes = [ctypes.POINTER(NconvSmoothLoss), P, P, ctypes.c_size_t, P, P]
     lib.nconv_edge_weights.restype = I
     lib.nconv_edge_weights.argtypes = [ctypes.POINTER(NconvEdgeWeights), P, P]
+    lib.nconv_depth_consistency.restype = I
+    lib.nconv_depth_consistency.argtypes = [ctypes.POINTER(NconvViewWarp), ctypes.POINTER(NconvConsistencySource), I,
+                                            F, F, I, P, P, P, P, P, P]
+    lib.nconv_geo_consistency_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_geo_consistency_workspace_bytes.argtypes = [I, I, I]
+    lib.nconv_geo_consistency_loss_fwd.restype = I
+    lib.nconv_geo_consistency_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, P, ctypes.c_size_t, P]
+    lib.nconv_geo_consistency_loss_bwd.restype = I
+    lib.nconv_geo_consistency_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, ctypes.c_size_t, P, P]
 
 
 def lib():

@@ -1,4 +1,5 @@
-// capi_common.h — what the extern "C" boundary files (nconv_capi.hip, capi_dense.hip, capi_io.hip) share:
+// capi_common.h — what the extern "C" boundary files (nconv_capi.hip, capi_dense.hip, capi_io.hip,
+// capi_consistency.hip) share:
 // the error text, the launch helper, and the checks of a caller's strided views. The boundary is host
 // code only: it validates, fills the launchers' argument structs (nconv_internal.h) and calls a launcher;
 // it starts no kernel and calls no runtime function itself.
@@ -20,6 +21,11 @@ int launched(const char* fn, Launch launch, const Args&... args) {
     const int rc = launch(args..., &why);
     return rc ? fail(rc, fn, why) : 0;
 }
+
+// The descriptor of the view-warp family checked and turned into the kernels' arguments, and the agreement of
+// the S views of one call in what they share (capi_io.hip): NULL, or the reason (kept in text where composed).
+const char* warp_args(const nconv_view_warp* d, WarpArgs& a, std::string& text);
+const char* views_agree(const nconv_view_warp* views, int S, std::string& text);
 
 // ---- buffer views: 32-bit offsets inside an image, read through a PlaneView (plane_io.h) ------------
 // The three reasons a view can be refused, in one entry point's wording.

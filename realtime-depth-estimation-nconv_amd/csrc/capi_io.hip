@@ -732,8 +732,11 @@ static const char* warp_image_view(const char* name, const float* base, int B, i
     return nullptr;
 }
 
-// The descriptor of nconv_view_warp_* / nconv_photo_loss_* checked and turned into the kernels' arguments.
-static const char* warp_args(const nconv_view_warp* d, nconv::WarpArgs& a, std::string& text) {
+}  // extern "C"
+
+// The descriptor of nconv_view_warp_* / nconv_photo_loss_* checked and turned into the kernels' arguments
+// (declared in capi_common.h: capi_consistency.hip checks its views by it too).
+const char* nconv::capi::warp_args(const nconv_view_warp* d, nconv::WarpArgs& a, std::string& text) {
     if (!d) return "null descriptor";
     if (!d->depth || !d->src || !d->k || !d->m) return "null depth, src, k or m";
     if (d->C != 1 && d->C != 3) return "C must be 1 or 3";
@@ -769,6 +772,35 @@ static const char* warp_args(const nconv_view_warp* d, nconv::WarpArgs& a, std::
     a.z_min = d->z_min, a.z_max = z_max;
     return nullptr;
 }
+
+// NULL, or how view s differs from view 0 in what the views of one call share (kept in text).
+const char* nconv::capi::views_agree(const nconv_view_warp* views, int S, std::string& text) {
+    const nconv_view_warp& d = views[0];
+    for (int s = 1; s < S; ++s) {
+        const nconv_view_warp& e = views[s];
+        const char* what = nullptr;
+        if (e.B != d.B || e.C != d.C || e.H != d.H || e.W != d.W)
+            what = "B, C, H or W";
+        else if (e.depth != d.depth || e.depth_row_stride != d.depth_row_stride ||
+                 (d.B > 1 && e.depth_image_stride != d.depth_image_stride))
+            what = "the depth view";
+        else if (e.mask != d.mask ||
+                 (d.mask && (e.mask_row_stride != d.mask_row_stride ||
+                             (d.B > 1 && e.mask_image_stride != d.mask_image_stride))))
+            what = "the mask view";
+        else if (e.k != d.k || e.k_image_stride != d.k_image_stride)
+            what = "k";
+        else if (!(e.z_min == d.z_min && e.z_max == d.z_max))
+            what = "z_min or z_max";
+        if (what) {
+            text = "view " + std::to_string(s) + " differs from view 0 in " + what;
+            return text.c_str();
+        }
+    }
+    return nullptr;
+}
+
+extern "C" {
 
 int nconv_view_warp_fwd(const struct nconv_view_warp* d, float* warped, unsigned char* valid, void* stream) {
     const char* fn = "nconv_view_warp_fwd";
@@ -908,27 +940,7 @@ static const char* min_args(const nconv_view_warp* views, int S, const float* tg
         }
     }
     const nconv_view_warp& d = views[0];
-    for (int s = 1; s < S; ++s) {
-        const nconv_view_warp& e = views[s];
-        const char* what = nullptr;
-        if (e.B != d.B || e.C != d.C || e.H != d.H || e.W != d.W)
-            what = "B, C, H or W";
-        else if (e.depth != d.depth || e.depth_row_stride != d.depth_row_stride ||
-                 (d.B > 1 && e.depth_image_stride != d.depth_image_stride))
-            what = "the depth view";
-        else if (e.mask != d.mask ||
-                 (d.mask && (e.mask_row_stride != d.mask_row_stride ||
-                             (d.B > 1 && e.mask_image_stride != d.mask_image_stride))))
-            what = "the mask view";
-        else if (e.k != d.k || e.k_image_stride != d.k_image_stride)
-            what = "k";
-        else if (!(e.z_min == d.z_min && e.z_max == d.z_max))
-            what = "z_min or z_max";
-        if (what) {
-            text = "view " + std::to_string(s) + " differs from view 0 in " + what;
-            return text.c_str();
-        }
-    }
+    if (const char* why = views_agree(views, S, text)) return why;
     if (automask)
         for (int s = 0; s < S; ++s)
             if (views[s].Hs != d.H || views[s].Ws != d.W) {

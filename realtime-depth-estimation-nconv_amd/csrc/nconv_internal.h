@@ -505,6 +505,26 @@ int launch_photo_min_loss_fwd(const MinArgs& m, float* loss, unsigned char* winn
 int launch_photo_min_loss_bwd(const MinArgs& m, const float* gloss, const void* ws, float* g_depth, hipStream_t st,
                               const char** why);
 
+// Cross-view depth consistency: the check with fusion and the geometry-consistency loss
+// (nconv_depth_consistency, nconv_geo_consistency_loss_*), consistency.hip.
+struct ConsistencyArgs {
+    WarpArgs v[kMinSources];          // the S sources, src = the source's depth plane (C == 1); they differ in
+                                      // src, Hs, Ws, m and mbs alone
+    const float* k_src[kMinSources];  // 3 x 3 of the source camera, images ksbs floats apart (0: one camera)
+    long long ksbs[kMinSources];
+    const float* m_back[kMinSources]; // 3 x 4, K_tgt . [R | t]^-1, images mbbs floats apart (0: one matrix)
+    long long mbbs[kMinSources];
+    int S, min_views;
+    float px_tol, rel_tol;
+};
+size_t geo_consistency_workspace_bytes(int B, int H, int W);
+int launch_depth_consistency(const ConsistencyArgs& m, float* fused, unsigned char* count, unsigned char* views,
+                             float* reproj, float* reldiff, hipStream_t st, const char** why);
+int launch_geo_consistency_loss_fwd(const WarpArgs& a, float* loss, float* diff, void* ws, hipStream_t st,
+                                    const char** why);
+int launch_geo_consistency_loss_bwd(const WarpArgs& a, const float* gloss, const void* ws, float* g_depth,
+                                    hipStream_t st, const char** why);
+
 // Relative pose by direct image alignment (nconv_pose_normal_eq, nconv_pose_update), pose_align.hip.
 constexpr int kPoseSums = 28;  // 21 of the upper triangle of sum w J^T J, 6 of sum w J r, sum w r^2
 struct PoseArgs {
