@@ -1883,6 +1883,97 @@ typedef struct nconv_edge_weights {
  * weights overlapping the image. */
 int nconv_edge_weights(const struct nconv_edge_weights* d, float* weights, void* stream);
 
+/* Voxel-grid merge of point clouds (new entry points only: no existing struct or signature changes, so
+ * NCONV_ABI_VERSION stays 27). The step after nconv_backproject_points, nconv_pose_* and nconv_depth_consistency:
+ * the clouds of several frames, each with the pose of its camera in the world, become ONE cloud with one point
+ * per occupied cell of a stated box of cubic cells: the weighted mean of the points that fell into the cell
+ * (Open3D's voxel_down_sample, PCL's VoxelGrid). The rule, fp32 with one rounding per operation unless it says
+ * double, no fused multiply-add anywhere:
+ *
+ *  rows      xyz is N rows of three fp32. With offsets (S + 1 int32, non-decreasing: the offsets of
+ *            nconv_backproject_points) row i belongs to segment s iff offsets[s] <= i < offsets[s + 1]; a row
+ *            below offsets[0] or at or beyond offsets[S] belongs to no segment (offsets[S] may exceed N: a
+ *            truncated cloud; rows at or beyond N do not exist). The segment is found by bisection: the number
+ *            of offsets <= i, minus one; with offsets that decrease somewhere a row still gets one of the S
+ *            segments or none, which of them is then unspecified. Without offsets every row is in segment 0.
+ *  1 world   with poses ((S, 3, 4) fp32 [R | t] of segment s, camera to world), row x = (x0, x1, x2) becomes
+ *            p_k = ((R_k0 x0 + R_k1 x1) + R_k2 x2) + t_k, five roundings, the order of nconv_view_warp_*'s and
+ *            nconv_lidar_project's 3 x 4 products; its normal n becomes (R_k0 n0 + R_k1 n1) + R_k2 n2. Without
+ *            poses p = x and the normal stays, bit for bit (no arithmetic).
+ *  2 cell    per axis a: f_a = floorf((p_a - origin_a) / voxel), one subtraction and one IEEE division. The
+ *            point is INSIDE iff it belongs to a segment, its weight (weights[i], 1 without weights) is > 0, and
+ *            f_a >= 0 && f_a < (float)n_a on all three axes: float comparisons before any conversion, so a NaN or
+ *            an infinite coordinate is not inside. A point on the box's lower faces is inside, one on its upper
+ *            faces is not. Every other row is DROPPED and counted; that includes a weight <= 0 (a negative
+ *            weight cannot be refused on the host without reading device memory, so it is dropped, not an
+ *            error). key = (i_z * ny + i_y) * nx + i_x with i_a = (int)f_a.
+ *  3 order   the inside points are sorted by key, stably: equal keys stay in ascending input row.
+ *            P = ceil(bits(nx * ny * nz - 1) / 8) radix passes of 8-bit digits, known from dims alone.
+ *  4 sums    a run is a maximal stretch of equal keys in the sorted order; it becomes one output row. W = the
+ *            sum of the run's weights in int64. For each of the up to nine values v of a point (p, the colour
+ *            bytes as numbers, the rotated normal) the run's sum of the terms (double)w * (double)v (one
+ *            rounding: the product is not exact for large weights) is taken in double in this tree: the sorted
+ *            positions 0, 1, .. are cut into chunks of C = 256. The part of a run inside one chunk is a piece;
+ *            a piece's sum is 0.0 + t_first + .. + t_last, left to right. The run's sum is its pieces' sums
+ *            added left to right, starting from the first piece's sum. The tree depends on sorted positions
+ *            only; one thread adds at most C terms and N / C pieces.
+ *  5 output  row m of the outputs is the run with the m-th smallest key:
+ *            xyz[m][a]     = (float)(sum of w p_a / (double)W)         (double division, then one rounding)
+ *            rgb[m][a]     = (uint8)rint(sum of w c_a / (double)W)      half to even; always inside [0, 255]
+ *            normals[m]    = the three sums rounded to fp32 (s_x, s_y, s_z), then l = sqrt((s_x s_x + s_y s_y) +
+ *                            s_z s_z) and s / l, exactly nconv_depth_normals' last step; (0, 0, 0) unless
+ *                            l > 0 && l < inf. A point whose normal is (0, 0, 0) ("none") adds zeros: it does not
+ *                            move the direction.
+ *            count[m]      = min(W, INT32_MAX);  key[m] = the run's key
+ *            stats         = int32 {n_voxels, n_inside, n_dropped, 0}, n_inside + n_dropped = N. n_voxels is the
+ *                            true number of runs even where it exceeds max_voxels; rows from
+ *                            min(n_voxels, max_voxels) on are not written.
+ *
+ * The result is a function of the inputs alone: the same bits on every run. 5 + 2 P launches on `stream`
+ * whatever the data (nx ny nz = 1: five), no global or floating-point atomics, no host synchronisation, no
+ * allocation: capturable in a hipGraph. Sized for the clouds of tens of frames: every workgroup of the compaction
+ * sums all N / 1024 tile counts for its base and one workgroup scans the N / 256 chunk counts, so up to N of
+ * some 10^7 rows these steps are a small share; the result stays right up to the limit N < 2^31, but there
+ * they take far longer than the rest. A merged map goes back in as a segment of its own with
+ * weights = count to add further clouds; that is a second application of the rule (the stored means were
+ * rounded to fp32), not bit-equal to one merge of everything. */
+typedef struct nconv_voxel_merge_args {
+    long long n_points;             /* N, 0 <= N < 2^31                                              */
+    const float* xyz;               /* (N, 3) fp32 (may be NULL when N == 0)                         */
+    long long xyz_row_stride;       /* elements, >= 3                                                */
+    const unsigned char* rgb;       /* NULL: no colours; (N, 3) uint8                                */
+    long long rgb_row_stride;       /* bytes, >= 3                                                   */
+    const float* normals;           /* NULL: no normals; (N, 3) fp32, (0, 0, 0) = none               */
+    long long normals_row_stride;   /* elements, >= 3                                                */
+    const int* weights;             /* NULL: every weight 1; (N) int32 contiguous                    */
+    const int* offsets;             /* NULL: one segment of all rows; (n_segments + 1) int32         */
+    const float* poses;             /* NULL: identity; (n_segments, 3, 4) fp32 contiguous            */
+    int n_segments;                 /* S >= 1; 1 without offsets                                     */
+    int nx, ny, nz;                 /* cells per axis, 1 <= nx * ny * nz < 2^31                      */
+    float voxel;                    /* edge of a cell, > 0 and finite                                */
+    float origin[3];                /* the box's lower corner, finite                                */
+    long long max_voxels;           /* rows of the outputs, 0 <= max_voxels < 2^31                   */
+    float* out_xyz;                 /* (max_voxels, 3) fp32 contiguous                               */
+    unsigned char* out_rgb;         /* (max_voxels, 3) uint8; required with rgb, else not written    */
+    float* out_normals;             /* (max_voxels, 3) fp32; required with normals, else not written */
+    int* out_count;                 /* (max_voxels) int32                                            */
+    int* out_key;                   /* (max_voxels) int32                                            */
+    int* stats;                     /* 4 int32                                                       */
+} nconv_voxel_merge_desc;
+
+/* workspace: nconv_voxel_merge_workspace_bytes(n_points, nx, ny, nz) bytes, 8-byte aligned, non-decreasing in
+ * n_points (0: n_points < 0 or >= 2^31, a dimension <= 0, or nx * ny * nz >= 2^31). With max_voxels == 0 the
+ * five out_* pointers are not read. The outputs are OVERWRITTEN and must not overlap the inputs.
+ * -EINVAL before any launch: a NULL descriptor or stats; n_points or max_voxels negative or >= 2^31; NULL xyz
+ * with n_points > 0; a row stride below 3 (or negative); a pointer that is not aligned to its element;
+ * n_segments < 1, or != 1 without offsets; a dimension <= 0 or nx * ny * nz >= 2^31; voxel not > 0 or not
+ * finite; an origin that is not finite; with max_voxels > 0 a NULL out_xyz, out_count or out_key, a NULL
+ * out_rgb with rgb, a NULL out_normals with normals; a workspace that is NULL, too small or not 8-byte
+ * aligned. */
+size_t nconv_voxel_merge_workspace_bytes(long long n_points, int nx, int ny, int nz);
+int nconv_voxel_merge(const struct nconv_voxel_merge_args* a, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

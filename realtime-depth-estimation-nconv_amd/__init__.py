@@ -40,8 +40,11 @@ from .smooth import EdgeWeights, Smoother, SmoothnessLoss, edge_weights, smoothn
 from . import consistency
 from .consistency import (DepthFuser, GeometryConsistency, GeometryConsistencyLoss, depth_consistency,
                           geometry_consistency_loss, inverse_pose)
+from . import voxelmap
+from .voxelmap import VoxelMap, VoxelMerger, voxel_merge
 
-__all__ = ["DepthFuser", "GeometryConsistency", "GeometryConsistencyLoss", "depth_consistency",
+__all__ = ["VoxelMap", "VoxelMerger", "voxel_merge",
+           "DepthFuser", "GeometryConsistency", "GeometryConsistencyLoss", "depth_consistency",
            "geometry_consistency_loss", "inverse_pose", "EstimatePose", "PoseEstimator", "estimate_pose", "pool_sparse", "pose_projection", "pose_step",
            "EdgeWeights", "Smoother", "SmoothnessLoss", "edge_weights", "smoothness_loss", "halve_intrinsics",
            "halve_projection", "MinReprojectionLoss", "MinReprojector", "min_reprojection_loss", "PhotometricLoss", "ViewWarper", "photometric_loss", "photometric_ssim_loss", "view_warp", "warp_projection", "ConfidenceLoss", "ConfLossFn", "confidence_loss", "NearestFill", "NearestFiller", "NearestSample", "nearest_sample",

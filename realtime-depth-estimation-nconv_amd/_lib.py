@@ -130,6 +130,8 @@ EXPORTED = (
     "nconv_geo_consistency_workspace_bytes",
     "nconv_geo_consistency_loss_fwd",
     "nconv_geo_consistency_loss_bwd",
+    "nconv_voxel_merge_workspace_bytes",
+    "nconv_voxel_merge",
 )
 
 
@@ -331,6 +333,17 @@ class NconvPoseAlign(ctypes.Structure):
         ("min_points", ctypes.c_int)]
 
 
+class NconvVoxelMerge(ctypes.Structure):
+    _fields_ = [("n_points", ctypes.c_longlong), ("xyz", ctypes.c_void_p), ("xyz_row_stride", ctypes.c_longlong),
+                ("rgb", ctypes.c_void_p), ("rgb_row_stride", ctypes.c_longlong), ("normals", ctypes.c_void_p),
+                ("normals_row_stride", ctypes.c_longlong), ("weights", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("poses", ctypes.c_void_p), ("n_segments", ctypes.c_int), ("nx", ctypes.c_int), ("ny", ctypes.c_int),
+                ("nz", ctypes.c_int), ("voxel", ctypes.c_float), ("origin", ctypes.c_float * 3),
+                ("max_voxels", ctypes.c_longlong), ("out_xyz", ctypes.c_void_p), ("out_rgb", ctypes.c_void_p),
+                ("out_normals", ctypes.c_void_p), ("out_count", ctypes.c_void_p), ("out_key", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -517,6 +530,10 @@ def _declare(lib):
     lib.nconv_geo_consistency_loss_fwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, P, ctypes.c_size_t, P]
     lib.nconv_geo_consistency_loss_bwd.restype = I
     lib.nconv_geo_consistency_loss_bwd.argtypes = [ctypes.POINTER(NconvViewWarp), P, P, ctypes.c_size_t, P, P]
+    lib.nconv_voxel_merge_workspace_bytes.restype = ctypes.c_size_t
+    lib.nconv_voxel_merge_workspace_bytes.argtypes = [L, I, I, I]
+    lib.nconv_voxel_merge.restype = I
+    lib.nconv_voxel_merge.argtypes = [ctypes.POINTER(NconvVoxelMerge), P, ctypes.c_size_t, P]
 
 
 def lib():

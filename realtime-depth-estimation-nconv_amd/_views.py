@@ -1,5 +1,5 @@
 """Argument checks shared by the modules that hand tensors to libnconv's I/O entry points
-(metrics, frames, pointcloud, lidar, visualize, sparsify, occlusion, sparsification, ipbasic, nearest): what a strided view of planes
+(metrics, frames, pointcloud, lidar, visualize, sparsify, occlusion, sparsification, ipbasic, nearest, voxelmap): what a strided view of planes
 is on the Python side.
 
 Every helper takes the calling module's `prefix` ("frames", "depth metrics", ...), so the text of an

@@ -88,4 +88,16 @@ __device__ __forceinline__ void project(const Camera& c, int i, int j, float z, 
     y = vz / c.fy;
 }
 
+// n = c / l with l = sqrt((c.x c.x + c.y c.y) + c.z c.z): one fp32 rounding per operation, division and square
+// root correctly rounded. True iff c has a direction: l > 0 && l < inf (normals.hip's unit normals, and the
+// mean normal of voxel_merge.hip)
+__device__ __forceinline__ bool unit_vector(float cx, float cy, float cz, float (&n)[3]) {
+#pragma clang fp contract(off)
+    const float xx = cx * cx, yy = cy * cy, zz = cz * cz;
+    const float xy = xx + yy;
+    const float len = sqrtf(xy + zz);  // the correctly rounded one (__fsqrt_rn is the hardware's approximation here)
+    n[0] = __fdiv_rn(cx, len), n[1] = __fdiv_rn(cy, len), n[2] = __fdiv_rn(cz, len);
+    return len > 0.f && len < __builtin_inff();
+}
+
 }  // namespace nconv

@@ -1,5 +1,5 @@
 // capi_common.h — what the extern "C" boundary files (nconv_capi.hip, capi_dense.hip, capi_io.hip,
-// capi_consistency.hip) share:
+// capi_consistency.hip, capi_voxel.hip) share:
 // the error text, the launch helper, and the checks of a caller's strided views. The boundary is host
 // code only: it validates, fills the launchers' argument structs (nconv_internal.h) and calls a launcher;
 // it starts no kernel and calls no runtime function itself.

@@ -563,4 +563,28 @@ struct EdgeArgs {
 };
 int launch_edge_weights(const EdgeArgs& a, float* w, hipStream_t st, const char** why);
 
+// Voxel-grid merge of point clouds (nconv_voxel_merge), voxel_merge.hip.
+struct VoxelArgs {
+    long long N;                 // rows of the inputs, 0 <= N < 2^31
+    const float* xyz;            // (N, 3) fp32, rows xs floats apart
+    long long xs;
+    const unsigned char* rgb;    // null: none; (N, 3) uint8, rows cs bytes apart
+    long long cs;
+    const float* nrm;            // null: none; (N, 3) fp32, rows ns floats apart
+    long long ns;
+    const int* w;                // null: every weight 1; (N)
+    const int* offsets;          // null: one segment of all rows; (S + 1)
+    const float* poses;          // null: identity; (S, 3, 4) contiguous
+    int S, nx, ny, nz;
+    float voxel, ox, oy, oz;
+    long long cap;               // rows of the outputs
+    float* oxyz;                 // (cap, 3)
+    unsigned char* orgb;         // (cap, 3), with rgb
+    float* onrm;                 // (cap, 3), with nrm
+    int *ocount, *okey;          // (cap)
+    int* stats;                  // (4)
+};
+size_t voxel_merge_workspace_bytes(long long N);
+int launch_voxel_merge(const VoxelArgs& a, void* ws, hipStream_t st, const char** why);
+
 }  // namespace nconv

@@ -70,11 +70,8 @@ __device__ __forceinline__ bool normal_of(const NormalsArgs& o, bool vc, const P
     const float dxy = dx + dy;
     const float dot = dxy + dz;
     if (dot > 0.f) cx = -cx, cy = -cy, cz = -cz;
-    const float xx = cx * cx, yy = cy * cy, zz = cz * cz;
-    const float xy = xx + yy;
-    const float len = sqrtf(xy + zz);  // the correctly rounded one (__fsqrt_rn is the hardware's approximation here)
-    n[0] = __fdiv_rn(cx, len), n[1] = __fdiv_rn(cy, len), n[2] = __fdiv_rn(cz, len);
-    return vc && (ul || ur) && (ut || ud) && len > 0.f && len < __builtin_inff();
+    const bool unit = unit_vector(cx, cy, cz, n);  // backproject_common.h
+    return vc && (ul || ur) && (ut || ud) && unit;
 }
 
 // clamp(rintf((0.5 + s * t * 0.5) * 255), 0, 255), s = +1 / -1: the products with 0.5 and -1 are exact
